@@ -22,9 +22,15 @@ torch.cuda.synchronize(), MAX over ranks.
 With N > 1 the step runs lookahead-parallel (window columns + candidates sharded over the ranks, one RCCL all-gather of a small
 int32 record per step; lade/decoding.py:973-986, 1088-1107): total work per step is fixed, so scaling is "strong".
 
-Prints ONE JSON line (rank 0): the driver's contract plus `roofline` (the attention launch pair: algorithmic bytes / live hipEvent
-timing; MFMA fraction beside it), `prefill`, `plain_decode`, `hot_regime` and `cpu_baseline` (the CPU oracle = a port of the
-reference's path, timed on this box's host cores on a bounded sample).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the driver's contract (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) with `config`, `step_compression`, `prefill` (measured during the setup) and
+`step_stream`.  `--full` adds what takes runs of its own: `spread` (--blocks - 1 more blocks of K steps), `roofline` (the attention launch
+pair: algorithmic bytes / live hipEvent timing; MFMA fraction beside it), `plain_decode`, `mid_regime`, `hot_regime`, `step_gpu_only`,
+`projections`, `via_generate`, `lp_default` (N > 1) and `cpu_baseline` (the CPU oracle = a port of the reference's path, timed on this
+box's host cores on a bounded sample).
+
+`--dump-outputs DIR` writes what the timed steps computed (dump_outputs below) as .npy files: with the same arguments the inputs (seeded
+weights, prompt and window) are the same from run to run, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -77,8 +83,23 @@ def parse(argv=None):
     ap.add_argument("--no-generate", action="store_true", help="skip the via_generate leg (tokens/s through lade.augment_all() + USE_LADE=1 model.generate() on an HF module)")
     ap.add_argument("--generate-tokens", type=int, default=256)
     ap.add_argument("--cpu-baseline-steps", type=int, default=3)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps: the first is the reported value, the others give the spread")
+    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps: the first is the reported value, the others give the spread (--full only)")
+    ap.add_argument("--full", action="store_true", help="also the measurements beyond the headline figure: spread blocks, roofline, plain decoding, "
+                    "mid / hot regimes, host turn-around, projections, via_generate, lp_default, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed steps computed to DIR/<name>.npy (float64)")
     return ap.parse_args(argv)
+
+
+def dump_outputs(directory, tokens, tok0, infos):
+    """What a caller of the timed path receives, as float64 arrays (token ids are exact in float64): the token stream the K timed steps
+    emitted, the tokens the last timed step accepted, and that step's record (max_hit, cache length after it, candidates for the next step)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    last = infos[-1]
+    arrays = {"timed_tokens": tokens[tok0:], "last_step_accepted": last["accepted"],
+              "last_step_record": [last.get("max_hit", -1), last.get("P_after", -1), last.get("g_next", -1)]}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def attn_algorithmic_bytes(cfg, T, P, elem=2):
@@ -392,6 +413,7 @@ def worker(args):
     W, N, G = c["W"], c["N"], c["G"]
     gs = N - 1
     GD_PAIRS = 5                                                   # with / without-attention block pairs of the step-time difference
+    # the cache is sized for a --full run in either mode: its capacity is the stride of its rows, so a plain run times the same layout
     total_steps = (N - 1) + args.warmup + args.steps * (max(1, args.blocks) + GD_PAIRS + 10) + 64
     max_seq = args.prompt_len + total_steps * N + (N - 1) * (W + G) + 64
     if int(os.environ.get("WORLD_SIZE", 1)) > 1:                  # + the reference-default configuration run by the same ranks (lp_default)
@@ -476,12 +498,14 @@ def worker(args):
         elapsed, prefill_s = float(tmax[0].item()), float(tmax[1].item())
     new_tokens = len(run.tokens) - tok0
     S = new_tokens / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run.tokens, tok0, infos)
     # the contract's number is the block above (exactly K steps).  Four more blocks of K steps follow for the spread: the boxes of the
     # pool drift by several per cent between consecutive runs of one binary, a single 80 ms block says nothing about that
     block_ms = [elapsed / args.steps * 1e3]
     block_max = [None]                                            # [slowest step (ms, host clock), its index] of the blocks after the contract's
     block_T = [round(sum((i.get("T") or 0) for i in infos) / max(1, len(infos)), 1)]      # rows fed per step: a block whose steps carry candidates feeds more
-    for _ in range(max(0, args.blocks - 1)):
+    for _ in range(max(0, args.blocks - 1) if args.full else 0):
         sync()
         tb0 = time.perf_counter()
         binf, marks = [], [tb0]
@@ -507,12 +531,12 @@ def worker(args):
     Ts = [i["T"] for i in infos if i.get("T")]
     avg_T = (sum(Ts) / len(Ts)) if Ts else float((N - 1) * W)
     P_end = run.P
-    extras = rank == 0 and not use_lp and not sampling and not args.no_extras
+    extras = args.full and rank == 0 and not use_lp and not sampling and not args.no_extras
 
     # ---- the attention launch pair timed IN the step: a few more steady steps, eager, with a hipEvent before the attention launch
     # and after the split merge of every layer (torch's current stream is the launch stream) ----
     in_situ = None
-    if not args.no_extras:                           # every rank takes the steps (the step's collective needs them all), rank 0 records
+    if args.full and not args.no_extras:             # every rank takes the steps (the step's collective needs them all), rank 0 records
         was_graph, dec.use_graph = dec.use_graph, False
         run.step()                                   # first eager step: one-off costs (autotune of a new row class ...)
         sync()
@@ -524,7 +548,7 @@ def worker(args):
         sync()
         eager_ms = (time.perf_counter() - te0) / 4 * 1e3
         evs, eng.attn_events, dec.use_graph = eng.attn_events, None, was_graph
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         T_ref = int(round(avg_T)) if not use_lp else (evs[-1][2] if evs else 0)     # LP: the rank's own shard width
         evs = [e for e in evs if e[2] == T_ref] or evs           # launches of the steady shape only (a stray candidate changes T)
         durs = sorted(e0.elapsed_time(e1) * 1e3 for (e0, e1, _, _) in evs)
@@ -896,7 +920,7 @@ def worker(args):
     # the default configuration feeds 420-840 rows on one rank and is what lookahead parallelism shards.  Both in ONE line, so that a
     # scaling run yields both curves.
     lp_default = None
-    if use_lp and world > 1 and not sampling and os.environ.get("LADE_BENCH_LP_DEFAULT", "1") != "0":
+    if args.full and use_lp and world > 1 and not sampling and os.environ.get("LADE_BENCH_LP_DEFAULT", "1") != "0":
         from lookaheaddecoding_amd.parallel import LPRunner as _LPR, shard_level_sizes as _sls, window_shard as _ws
         Wd, Nd, Gd = 60, 8, 60
         try:
@@ -930,55 +954,57 @@ def worker(args):
             print(f"[bench] lp_default failed: {e_}", file=sys.stderr, flush=True)
 
     if rank == 0:
-        # ---- roofline of the dominant hand-written kernel: lookahead attention, one layer ----
-        T_mid = int(round(avg_T))
-        if use_lp:                                   # a rank's own shard: re-derive it from the runner's partition
-            from lookaheaddecoding_amd.parallel import shard_level_sizes, window_shard
-            c0, c1 = window_shard(W, world, rank)
-            ls = shard_level_sizes([W - 1] + [W] * (N - 2), c0, c1)
-            g_mid = 0
-            mask = ops.StepMask.from_levels(1, ls, 0, gs, P_end)
-        else:
-            g_mid = max(0, (T_mid - (N - 1) * W) // gs)
-            mask = ops.StepMask.from_levels(1, [W - 1] + [W] * (N - 2), g_mid * gs, gs, P_end)
-        T_k = mask.T
-        qkv = torch.randn(T_k, (cfg["heads"] + 2 * cfg["kv_heads"]) * cfg["head_dim"], device=dev).to(dtype)
-        ns = eng.n_splits_for(T_k, P_end + T_k)
-        acfg_k = eng.attn_choice(T_k)
-        cls_k = next((c_ for c_ in eng.ROW_CLASSES if T_k <= c_), None)
-        # every repetition uses the next layer's K/V cache (L caches of 2*Hkv*S_max*d*e bytes >> the 256 MB Infinity Cache), so the
-        # launch streams its keys/values from HBM exactly as inside a decode step
-        us = ops.time_attn(qkv, [eng.k_cache(li) for li in range(eng.L)], [eng.vt_cache(li) for li in range(eng.L)], mask,
-                           H=cfg["heads"], Hkv=cfg["kv_heads"], d=cfg["head_dim"], n_splits=ns, reps=max(200, 8 * eng.L), wg_rows=acfg_k[1])
-        us_iso, how = us, "isolated (no in-step measurement in this mode)"
-        if graph_delta is not None and graph_delta["us"] > 0:
-            us, how = graph_delta["us"], "hipGraph step time with / without the attention launches"
-        elif in_situ is not None and abs(in_situ["T"] - T_k) <= gs and in_situ["gpu_bound"]:      # within one stray candidate of the steady shape
-            us, ns, how = in_situ["us"], in_situ["n_splits"], "hipEvents inside real decode steps, minus what an empty event bracket reads"
-        alg = attn_algorithmic_bytes(cfg, T_k, P_end)
-        flops = attn_useful_flops(cfg, T_k, P_end, W, N, g_mid) if not use_lp else 4 * cfg["head_dim"] * cfg["heads"] * T_k * P_end
-        achieved = alg / (us * 1e-6) / 1e9
-        traffic, traffic_source = pmc_traffic(cfg, T_k, P_end, ns, acfg_k[1])
-        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4),
-                    "traffic": traffic, "traffic_source": traffic_source,
-                    "kernel": f"lade::attn_fwd_kernel<{args.dtype},{cfg['head_dim']}> (+combine, n_splits={ns})",
-                    "launch_us": round(us, 2), "launch_us_source": how, "algorithmic_bytes": alg, "T": T_k, "P": P_end,
-                    "launch_parameters": {"rope_kv_append_fused_into_the_launch": bool(acfg_k[0]), "wg_rows": acfg_k[1] or 128, "n_splits": ns,
-                                          "split_mode": acfg_k[2], "decided_by": "StepEngine._refine_in_step (in-step autotune)" if cls_k in eng.step_tune_log else "default"},
-                    "launch_us_with_rope_append": None if graph_delta is None else round(graph_delta["us_with_rope_append"], 2),
-                    "mfma": {"useful_flops": flops, "achieved_tflops": round(flops / (us * 1e-6) / 1e12, 1), "peak_tflops": 2500.0,
-                             "frac": round(flops / (us * 1e-6) / 1e12 / 2500.0, 4),
-                             "note": "useful flops of the closed-form mask (SURVEY 8d) / the same launch time / dense bf16 MFMA peak; utilisation counters (SQ_VALU_MFMA_BUSY_CYCLES per launch, bench shapes c2 / c2 with candidates / c4 / c5): profiles/r3_pmc/attn_pmc_table.json"},
-                    "launch_us_in_step": None if in_situ is None else {k: (round(v, 2) if isinstance(v, float) else v) for k, v in in_situ.items()},
-                    "launch_us_graph_delta": None if graph_delta is None else {k: (round(v, 2) if isinstance(v, float) else v) for k, v in graph_delta.items()},
-                    "launch_us_isolated": round(us_iso, 2),
-                    "note": "launch_us = one layer's launch pair (attention + split merge) inside real decode steps: (hipGraph step time - the same step with "
-                            "the attention launches left out and RoPE + KV append as a launch of their own) / layers when that was measured (single GPU) - with the fused launch this is "
-                            "what the pair costs ON TOP of that launch, the quantity rounds 1-4 reported; launch_us_with_rope_append = the same difference against a step without "
-                            "attention, RoPE and append (round 4: 16.9 + 7.0 us as three launches); else the pair bracketed by hipEvents on the launch "
-                            "stream in 4 eager steady steps after the timed region, every layer, minus what an empty bracket - two events recorded back to back "
-                            "in the same place - reads (launch_us_in_step.empty_bracket_us; used when those steps are GPU bound); else isolated "
-                            "back-to-back launches cycling through the layers' K/V caches (every launch reads HBM)"}
+        roofline = None
+        if args.full:
+            # ---- roofline of the dominant hand-written kernel: lookahead attention, one layer ----
+            T_mid = int(round(avg_T))
+            if use_lp:                                   # a rank's own shard: re-derive it from the runner's partition
+                from lookaheaddecoding_amd.parallel import shard_level_sizes, window_shard
+                c0, c1 = window_shard(W, world, rank)
+                ls = shard_level_sizes([W - 1] + [W] * (N - 2), c0, c1)
+                g_mid = 0
+                mask = ops.StepMask.from_levels(1, ls, 0, gs, P_end)
+            else:
+                g_mid = max(0, (T_mid - (N - 1) * W) // gs)
+                mask = ops.StepMask.from_levels(1, [W - 1] + [W] * (N - 2), g_mid * gs, gs, P_end)
+            T_k = mask.T
+            qkv = torch.randn(T_k, (cfg["heads"] + 2 * cfg["kv_heads"]) * cfg["head_dim"], device=dev).to(dtype)
+            ns = eng.n_splits_for(T_k, P_end + T_k)
+            acfg_k = eng.attn_choice(T_k)
+            cls_k = next((c_ for c_ in eng.ROW_CLASSES if T_k <= c_), None)
+            # every repetition uses the next layer's K/V cache (L caches of 2*Hkv*S_max*d*e bytes >> the 256 MB Infinity Cache), so the
+            # launch streams its keys/values from HBM exactly as inside a decode step
+            us = ops.time_attn(qkv, [eng.k_cache(li) for li in range(eng.L)], [eng.vt_cache(li) for li in range(eng.L)], mask,
+                               H=cfg["heads"], Hkv=cfg["kv_heads"], d=cfg["head_dim"], n_splits=ns, reps=max(200, 8 * eng.L), wg_rows=acfg_k[1])
+            us_iso, how = us, "isolated (no in-step measurement in this mode)"
+            if graph_delta is not None and graph_delta["us"] > 0:
+                us, how = graph_delta["us"], "hipGraph step time with / without the attention launches"
+            elif in_situ is not None and abs(in_situ["T"] - T_k) <= gs and in_situ["gpu_bound"]:      # within one stray candidate of the steady shape
+                us, ns, how = in_situ["us"], in_situ["n_splits"], "hipEvents inside real decode steps, minus what an empty event bracket reads"
+            alg = attn_algorithmic_bytes(cfg, T_k, P_end)
+            flops = attn_useful_flops(cfg, T_k, P_end, W, N, g_mid) if not use_lp else 4 * cfg["head_dim"] * cfg["heads"] * T_k * P_end
+            achieved = alg / (us * 1e-6) / 1e9
+            traffic, traffic_source = pmc_traffic(cfg, T_k, P_end, ns, acfg_k[1])
+            roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4),
+                        "traffic": traffic, "traffic_source": traffic_source,
+                        "kernel": f"lade::attn_fwd_kernel<{args.dtype},{cfg['head_dim']}> (+combine, n_splits={ns})",
+                        "launch_us": round(us, 2), "launch_us_source": how, "algorithmic_bytes": alg, "T": T_k, "P": P_end,
+                        "launch_parameters": {"rope_kv_append_fused_into_the_launch": bool(acfg_k[0]), "wg_rows": acfg_k[1] or 128, "n_splits": ns,
+                                              "split_mode": acfg_k[2], "decided_by": "StepEngine._refine_in_step (in-step autotune)" if cls_k in eng.step_tune_log else "default"},
+                        "launch_us_with_rope_append": None if graph_delta is None else round(graph_delta["us_with_rope_append"], 2),
+                        "mfma": {"useful_flops": flops, "achieved_tflops": round(flops / (us * 1e-6) / 1e12, 1), "peak_tflops": 2500.0,
+                                 "frac": round(flops / (us * 1e-6) / 1e12 / 2500.0, 4),
+                                 "note": "useful flops of the closed-form mask (SURVEY 8d) / the same launch time / dense bf16 MFMA peak; utilisation counters (SQ_VALU_MFMA_BUSY_CYCLES per launch, bench shapes c2 / c2 with candidates / c4 / c5): profiles/r3_pmc/attn_pmc_table.json"},
+                        "launch_us_in_step": None if in_situ is None else {k: (round(v, 2) if isinstance(v, float) else v) for k, v in in_situ.items()},
+                        "launch_us_graph_delta": None if graph_delta is None else {k: (round(v, 2) if isinstance(v, float) else v) for k, v in graph_delta.items()},
+                        "launch_us_isolated": round(us_iso, 2),
+                        "note": "launch_us = one layer's launch pair (attention + split merge) inside real decode steps: (hipGraph step time - the same step with "
+                                "the attention launches left out and RoPE + KV append as a launch of their own) / layers when that was measured (single GPU) - with the fused launch this is "
+                                "what the pair costs ON TOP of that launch, the quantity rounds 1-4 reported; launch_us_with_rope_append = the same difference against a step without "
+                                "attention, RoPE and append (round 4: 16.9 + 7.0 us as three launches); else the pair bracketed by hipEvents on the launch "
+                                "stream in 4 eager steady steps after the timed region, every layer, minus what an empty bracket - two events recorded back to back "
+                                "in the same place - reads (launch_us_in_step.empty_bracket_us; used when those steps are GPU bound); else isolated "
+                                "back-to-back launches cycling through the layers' K/V caches (every launch reads HBM)"}
         mid = mid_regime(plain["ms_per_token"] if plain else None) if extras else None
         hot_l = hot_live() if extras else None
         hot = hot_regime() if extras else None          # last: it zeroes o_proj / down_proj
@@ -986,7 +1012,7 @@ def worker(args):
         if extras and not args.no_generate and world == 1 and not use_lp and cfg["layers"] * cfg["hidden"] <= 40 * 5120:        # (the 70B shape would need 2 x 140 GB beside this engine)
             gen_leg = via_generate(c, cfg, dtype, args.prompt_len, W, N, G, args.generate_tokens, elapsed / args.steps * 1e3, plain["ms_per_token"] if plain else None)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:            # the CPU baseline is timed at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N=1 only
             cpu = cpu_baseline(c, cfg, args.prompt_len, args.cpu_baseline_steps, allow_full=not args.layers)
         mode = "sampling (temperature %.2f)" % c["temperature"] if sampling else "greedy"
         # what the line's numbers rest on, where the driver's parser keeps it (`config`): the greedy-parity status of the 16-bit engine
@@ -1056,6 +1082,13 @@ def worker(args):
                             "note": "per rank; unavoidable reads of one decode step (every projection weight, the K/V cache, the lm_head) / ms_per_step"},
             "cpu_baseline": cpu, "via_generate": gen_leg,
         }
+        if not args.full:
+            # a plain run: the contract's block and what the setup measured anyway, nothing that takes runs of its own
+            for k in ("spread", "mid_regime", "hot_regime", "hot_regime_forced", "plain_decode", "step_gpu_only", "roofline", "cpu_baseline", "via_generate"):
+                del out[k]
+            for k in ("plain_decode_tokens_per_s", "lookahead_over_plain_step", "mid_regime", "via_generate", "spread_ms_per_step_blocks"):
+                del out["config"][k]
+            del out["config"]["parity"]["this_run"], out["parity"]["this_run_teacher_forced"]
         if lp_default is not None:
             out["lp_default"] = lp_default
         if use_lp and world > 1:
@@ -1068,7 +1101,7 @@ def worker(args):
         # weights; not the in-step time - the kernel trace under profiles/ has that): weight bytes / time against the same HBM peak
         cls_T = next((c_ for c_ in eng.ROW_CLASSES if int(round(avg_T)) <= c_), None)
         proj = {}
-        for nm in eng.LAYER_GEMMS:
+        for nm in (eng.LAYER_GEMMS if args.full else ()):
             tm = eng.gemm_times.get((nm, cls_T))
             if tm and tm[0]:
                 proj[nm] = {"us": round(tm[0] * 1e3, 2), "weight_mb": round(tm[1] / 1e6, 1), "tb_per_s": round(tm[1] / tm[0] / 1e9, 2),

@@ -117,3 +117,24 @@ def test_projections_object_of_the_committed_line_is_consistent():
     for n, e in t.items():
         assert e["ms_per_layer_in_step_choice"] <= e["ms_per_layer_isolated_choice"] + 1e-9 and e["candidates"] >= 2
         assert e["in_step_choice"] == p[n]["kernel"]
+
+
+def test_plain_and_full_options_and_the_output_dump(tmp_path):
+    """`--full` is off by default (a plain run measures only the headline figure); `--dump-outputs DIR` writes the timed path's
+    outputs as float64 .npy files: the timed token stream, the last step's accepted tokens and its record."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    tokens = [1, 5, 9, 17, 33, 40, 41, 42, 43, 44]
+    infos = [dict(accepted=[41, 42], max_hit=2, P_after=13, g_next=3), dict(accepted=[43, 44], max_hit=2, P_after=15, g_next=0)]
+    bench.dump_outputs(str(tmp_path / "out"), tokens, 6, infos)
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("timed_tokens", "last_step_accepted", "last_step_record")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["timed_tokens"].tolist() == [41, 42, 43, 44] and got["last_step_accepted"].tolist() == [43, 44]
+    assert got["last_step_record"].tolist() == [2, 15, 0]

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -52,7 +53,7 @@ def test_bench_spawns_its_own_ranks_and_prints_one_json_line_last():
     """`python bench.py --gpus N` without a launcher starts its ranks itself (torch.multiprocessing.spawn, one per GPU, RCCL between
     them).  One GPU here: the spawn path is exercised with one rank on the lookahead-parallel code path (real RCCL group), a reduced
     layer count, and the contract is checked on what it prints: the JSON line is the last line of stdout."""
-    out = _run(["bench.py", "--gpus", "1", "--force-lp", "--layers", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--prompt-len", "256"],
+    out = _run(["bench.py", "--gpus", "1", "--force-lp", "--layers", "2", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline", "--prompt-len", "256"],
                {"LADE_BENCH_FORCE_SPAWN": "1"})
     lines = [l for l in out.splitlines() if l.strip()]
     d = json.loads(lines[-1])
@@ -68,7 +69,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu():
     candidates sharded, one all-gather per step, GEMM choices of rank 0 adopted by rank 1, max-over-ranks timing).  Both ranks sit on the
     one GPU of this box, which RCCL refuses, so the process group is gloo here (LADE_BENCH_SHARE_GPU / LADE_BENCH_BACKEND, test-only
     switches); the token-level parity of the sharded step is pinned in test_gpu_lp.py / test_lp_gloo.py."""
-    out = _run(["bench.py", "--gpus", "2", "--layers", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--prompt-len", "256"],
+    out = _run(["bench.py", "--gpus", "2", "--layers", "2", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline", "--prompt-len", "256"],
                {"LADE_BENCH_SHARE_GPU": "1", "LADE_BENCH_BACKEND": "gloo"})
     lines = [l for l in out.splitlines() if l.strip()]
     d = json.loads(lines[-1])
@@ -93,10 +94,30 @@ def _check_multi_rank_line(d, R):
 def test_bench_eight_ranks_end_to_end_on_one_gpu():
     """the same with EIGHT ranks - the world size the driver's scaling run ends at: window columns 15 / 8 -> 2 per rank (the last rank gets 1),
     candidates sharded eight ways, rank 0's kernel decisions adopted by seven others; the line carries both configurations."""
-    out = _run(["bench.py", "--gpus", "8", "--layers", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--prompt-len", "256"],
+    out = _run(["bench.py", "--gpus", "8", "--layers", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--prompt-len", "256"],
                {"LADE_BENCH_SHARE_GPU": "1", "LADE_BENCH_BACKEND": "gloo"})
     lines = [l for l in out.splitlines() if l.strip()]
     d = json.loads(lines[-1])
     assert d["n_gpus"] == 8 and d["steps"] == 3 and d["config"]["parallelism"] == "lp8" and d["config"]["shared_gpu"] is True
     assert d["scaling"] == "strong" and d["value"] > 0 and d["roofline"]["bound"] == "hbm" and d["roofline"]["T"] <= 16
     _check_multi_rank_line(d, 8)
+
+
+def test_bench_plain_run_is_lean_and_its_outputs_repeat(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and prints the contract without the --full measurements; --dump-outputs writes
+    what the timed steps emitted, and a second run with the same arguments writes the same arrays (seeded weights, prompt and window)."""
+    outs = []
+    for i in range(2):
+        d_out = tmp_path / f"run{i}"
+        out = _run(["bench.py", "--gpus", "1", "--layers", "2", "--steps", "5", "--warmup", "2", "--prompt-len", "256", "--dump-outputs", str(d_out)], {})
+        d = json.loads([l for l in out.splitlines() if l.strip()][-1])
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "bf16"
+        assert d["unit"] == "tokens/s" and d["higher_is_better"] is True and "metric" in d
+        assert not {"roofline", "cpu_baseline", "spread", "plain_decode", "mid_regime", "hot_regime", "via_generate", "projections"} & set(d)
+        arrays = {n: np.load(d_out / f"{n}.npy") for n in ("timed_tokens", "last_step_accepted", "last_step_record")}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert len(arrays["timed_tokens"]) == round(d["step_compression"] * 5) and len(arrays["last_step_accepted"]) >= 1
+        assert list(arrays["timed_tokens"][-len(arrays["last_step_accepted"]):]) == list(arrays["last_step_accepted"])
+        outs.append(arrays)
+    for n in outs[0]:
+        assert np.array_equal(outs[0][n], outs[1][n]), n

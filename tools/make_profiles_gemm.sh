@@ -9,11 +9,11 @@ OUT=$ROOT/gpurun_out/r2
 mkdir -p $OUT $ROOT/gpurun_out/pmc
 export TMPDIR=/tmp
 for c in c2 c3 c4 c5; do
-    timeout 900 python bench.py --config $c --steps 32 --warmup 8 2> $OUT/bench_$c.err | grep "^{" > $OUT/bench_$c.json
+    timeout 900 python bench.py --full --config $c --steps 32 --warmup 8 2> $OUT/bench_$c.err | grep "^{" > $OUT/bench_$c.json
     echo "bench $c rc=$? $(cut -c1-140 $OUT/bench_$c.json)"
 done
 rm -rf /tmp/kt
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $ROOT/bench.py --steps 32 --warmup 8 --no-cpu-baseline --no-extras > /tmp/kt.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $ROOT/bench.py --full --steps 32 --warmup 8 --no-cpu-baseline --no-extras > /tmp/kt.log 2>&1)
 grep "^{" /tmp/kt.log > $OUT/bench_c2_under_rocprof.json
 cp $(find /tmp/kt -name "*kernel_stats.csv" | head -1) $OUT/bench_c2_kernel_stats.csv
 python tools/trace_medians.py $(find /tmp/kt -name "*kernel_trace.csv" | head -1) > $OUT/bench_c2_kernel_medians.txt

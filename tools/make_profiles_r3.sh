@@ -12,12 +12,12 @@ timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; rc=
 [ $rc -ne 0 ] && exit $rc
 # 1. bench lines, un-profiled: the default configuration with the CPU baseline, then the other configurations
 for c in c2 c3 c4 c5; do
-    timeout 1200 python bench.py --config $c --steps 32 --warmup 8 2> $OUT/bench_$c.err | grep "^{" > $OUT/bench_$c.json
+    timeout 1200 python bench.py --full --config $c --steps 32 --warmup 8 2> $OUT/bench_$c.err | grep "^{" > $OUT/bench_$c.json
     echo "bench $c rc=$? $(cut -c1-160 $OUT/bench_$c.json)"
 done
 # 2. kernel trace + stats of the default bench (profiled run: its own bench line is kept beside the trace)
 rm -rf /tmp/kt
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $ROOT/bench.py --steps 32 --warmup 8 --blocks 1 --no-cpu-baseline --no-extras > /tmp/kt.log 2>&1)
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $ROOT/bench.py --full --steps 32 --warmup 8 --blocks 1 --no-cpu-baseline --no-extras > /tmp/kt.log 2>&1)
 grep "^{" /tmp/kt.log > $OUT/bench_c2_under_rocprof.json
 cp $(find /tmp/kt -name "*kernel_stats.csv" | head -1) $OUT/bench_c2_kernel_stats.csv
 python tools/trace_medians.py $(find /tmp/kt -name "*kernel_trace.csv" | head -1) > $OUT/bench_c2_kernel_medians.txt

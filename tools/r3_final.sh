@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu_final.log 2>&1; echo "gpu suite rc=$?"; tail -4 $OUT/pytest_gpu_final.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 900 python bench.py > $OUT/bench_final.out 2> $OUT/bench_final.err; echo "bench rc=$?"; grep "^{" $OUT/bench_final.out > $OUT/bench_final.json
+timeout 900 python bench.py --full > $OUT/bench_final.out 2> $OUT/bench_final.err; echo "bench rc=$?"; grep "^{" $OUT/bench_final.out > $OUT/bench_final.json
 python - <<P
 import json
 d=json.load(open("$OUT/bench_final.json")); r=d["roofline"]
