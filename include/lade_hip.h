@@ -47,6 +47,9 @@
  *                            lade/models/modeling_llama.py:360-380 (MLP), :492-494, :558 (q/k/v/o)
  *   lade_rope_kv_append_parts / lade_add_rmsnorm_parts / lade_silu_mul_parts   the same glue ops taking that
  *                            GEMM's fp32 split-K partials as input (the reduction is fused into the consumer)
+ *   lade_rope_kv_append_ex / lade_rope_kv_append_parts_ex   the two RoPE + KV append entry points with the qkv epilogue of
+ *                            Qwen2 (q / k / v bias) and Qwen3 (per-head RMSNorm of q and k before RoPE); the reference adapts
+ *                            Llama only
  *   lade_time_attn / lade_time_attn_rot   hipEvent timing helpers for bench.py (no reference counterpart)
  */
 #ifndef LADE_HIP_H
@@ -425,6 +428,29 @@ int lade_rope_kv_append_parts(const float* parts, int32_t n_parts, int64_t part_
                               const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int32_t T, int32_t P,
                               const int32_t* dyn_P, int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos,
                               int32_t dtype, void* stream);
+/* ---- qkv epilogue of RoPE + KV append (Qwen2 / Qwen3; additive to ABI 3) -------------------------------------------
+ * Applied per token and head between the qkv projection and RoPE; a null field skips its step:
+ *   bias    [(H + 2*Hkv)*d] model dtype, added to q, k and v: to the fp32 sum of the partials before its single rounding
+ *           (lade_rope_kv_append_parts_ex: F.linear with a bias), to the already rounded projection with one more rounding
+ *           (lade_rope_kv_append_ex);
+ *   q_norm, k_norm   [d] model dtype: Qwen3RMSNorm over each q / k head, x -> round(w * round(x * rsqrt(mean(x^2) + eps))), the
+ *           mean in fp32; RoPE runs on the result.  V gets the bias only.
+ * All pointers 16-byte aligned.  A null `epi` (or one whose three pointers are null) launches exactly the plain kernel.  The
+ * head norm on the partials path needs d / 16 to be a power of two. */
+typedef struct lade_qkv_epilogue {
+    const void* bias;
+    const void* q_norm;
+    const void* k_norm;
+    float eps;
+} lade_qkv_epilogue;
+int lade_rope_kv_append_ex(void* qkv, const int32_t* positions, const void* cos_tab, const void* sin_tab,
+                           void* k_cache, void* vt_cache, int32_t T, int32_t P, const int32_t* dyn_P,
+                           int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
+                           const lade_qkv_epilogue* epi, void* stream);
+int lade_rope_kv_append_parts_ex(const float* parts, int32_t n_parts, int64_t part_stride, void* q_out, const int32_t* positions,
+                                 const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int32_t T, int32_t P,
+                                 const int32_t* dyn_P, int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos,
+                                 int32_t dtype, const lade_qkv_epilogue* epi, void* stream);
 int lade_splitk_reduce(const float* part, void* C, int64_t ldc, int32_t M, int32_t N, int32_t n_split, int32_t dtype,
                        void* stream);
 

@@ -56,6 +56,11 @@ class AttnArgs(C.Structure):
                 ("sync_flags", C.c_void_p)]
 
 
+class QkvEpilogue(C.Structure):
+    """lade_qkv_epilogue: bias of q / k / v and per-head RMSNorm of q / k between the qkv projection and RoPE (null = skipped)"""
+    _fields_ = [("bias", C.c_void_p), ("q_norm", C.c_void_p), ("k_norm", C.c_void_p), ("eps", C.c_float)]
+
+
 _lib: Optional[C.CDLL] = None
 
 _i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -106,6 +111,9 @@ SIGNATURES = {
     "lade_add_rmsnorm_parts": [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
     "lade_silu_mul_parts": [_vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
     "lade_rope_kv_append_parts": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "lade_rope_kv_append_ex": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(QkvEpilogue), _vp],
+    "lade_rope_kv_append_parts_ex": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                     C.POINTER(QkvEpilogue), _vp],
     "lade_splitk_reduce": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
     "lade_record_seal": [C.POINTER(C.c_uint32), C.c_uint32],
     "lade_version": [],

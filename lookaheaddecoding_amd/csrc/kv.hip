@@ -16,17 +16,35 @@ namespace lade {
 //                             A thread owns VEC consecutive pairs (i, i+d/2) of one head: 16-byte loads / stores.
 //   then n_vblk blocks      : V transpose.  Block (kv head, 64-token slab, 32-wide d chunk) stages the
 //                             slab through LDS and writes V^T[d][P+t] with the token index fastest.
-template <typename T>
+//
+// EPI: the qkv epilogue of lade_qkv_epilogue (Qwen2 / Qwen3), every step skipped where its pointer is null.  Per token and head:
+//   bias    added to q, k and v - to the fp32 sum of the partials before its one rounding (F.linear with a bias), or to the
+//           already rounded projection (materialised qkv) with a rounding of its own;
+//   norm    q rows with q_norm, k rows with k_norm, HF's Qwen3RMSNorm sequence: var = mean(x^2) in fp32, y = round(x * rsqrt(var + eps)),
+//           z = round(w * y); RoPE then runs on z.  The d/2 pairs of a head sit on vph consecutive lanes (vph a power of two on
+//           this path): the sum of squares is a __shfl_xor reduction over them.
+// EPI = false compiles to the plain kernel.
+template <typename S>
+struct QkvEpi {
+    const S* bias;
+    const S* qn;
+    const S* kn;
+    float eps;
+};
+
+template <typename T, bool EPI>
 __global__ __launch_bounds__(256) void rope_kv_append_kernel(typename Elem<T>::S* qkv, const int32_t* positions,
                                                              const typename Elem<T>::S* cos_tab,
                                                              const typename Elem<T>::S* sin_tab,
                                                              typename Elem<T>::S* k_cache, typename Elem<T>::S* vt_cache,
                                                              int T_, int P, const int32_t* dyn_P, int H, int Hkv, int d,
                                                              int S_max, int max_pos, const float* parts, int n_parts,
-                                                             size_t part_stride, typename Elem<T>::S* q_out, int bpt) {
+                                                             size_t part_stride, typename Elem<T>::S* q_out, int bpt,
+                                                             QkvEpi<typename Elem<T>::S> ep) {
     typedef typename Elem<T>::S S;
     constexpr int VEC = 16 / sizeof(S);
     __shared__ S sm[64][32 + 2];
+    const bool norm = EPI && (ep.qn || ep.kn);
     if (dyn_P) {
         P = *dyn_P;
         if (P + T_ > S_max) return;     // device-side cache length (hipGraph steps): never write K/V rows past the cache
@@ -41,8 +59,8 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(typename Elem<T>::S
         const S* s = sin_tab + (size_t)pos * d;
         const int half = d >> 1;
         S* row = qkv + (size_t)t * row_w;
-        if (half % VEC == 0) {
-            const int vph = half / VEC;                               // vectors per half head
+        const int vph = half / VEC;                                   // vectors per half head
+        if (half % VEC == 0 && (!norm || (vph & (vph - 1)) == 0)) {
             for (int idx = sub * blockDim.x + threadIdx.x; idx < (H + Hkv) * vph; idx += bpt * blockDim.x) {
                 const int h = idx / vph, i = (idx - h * vph) * VEC;
                 S* x = row + (size_t)h * d;
@@ -53,6 +71,17 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(typename Elem<T>::S
                 *reinterpret_cast<uint4*>(c2) = *reinterpret_cast<const uint4*>(c + i + half);
                 *reinterpret_cast<uint4*>(s1) = *reinterpret_cast<const uint4*>(s + i);
                 *reinterpret_cast<uint4*>(s2) = *reinterpret_cast<const uint4*>(s + i + half);
+                // ... and so do the epilogue's bias and norm weights
+                S b1[VEC], b2[VEC], w1[VEC], w2[VEC];
+                const S* nw = EPI ? (h < H ? ep.qn : ep.kn) : nullptr;          // uniform over the vph lanes of the head
+                if (EPI && ep.bias) {
+                    *reinterpret_cast<uint4*>(b1) = *reinterpret_cast<const uint4*>(ep.bias + (size_t)h * d + i);
+                    *reinterpret_cast<uint4*>(b2) = *reinterpret_cast<const uint4*>(ep.bias + (size_t)h * d + i + half);
+                }
+                if (EPI && nw) {
+                    *reinterpret_cast<uint4*>(w1) = *reinterpret_cast<const uint4*>(nw + i);
+                    *reinterpret_cast<uint4*>(w2) = *reinterpret_cast<const uint4*>(nw + i + half);
+                }
                 if (parts) {                       // qkv arrives as split-K fp32 partials: sum, round once to the dtype
                     const size_t e0 = (size_t)t * row_w + (size_t)h * d + i;
                     float a[VEC], b[VEC];
@@ -88,11 +117,40 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(typename Elem<T>::S
                     if (n_parts <= 2) sum_parts(std::integral_constant<int, 2>{});
                     else if (n_parts <= 4) sum_parts(std::integral_constant<int, 4>{});
                     else sum_parts(std::integral_constant<int, 8>{});
+                    if (EPI && ep.bias) {              // the bias joins the fp32 sum before its one rounding
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) { a[e] += Elem<T>::ld(b1[e]); b[e] += Elem<T>::ld(b2[e]); }
+                    }
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) { x1[e] = Elem<T>::st(a[e]); x2[e] = Elem<T>::st(b[e]); }
                 } else {
                     *reinterpret_cast<uint4*>(x1) = *reinterpret_cast<const uint4*>(x + i);
                     *reinterpret_cast<uint4*>(x2) = *reinterpret_cast<const uint4*>(x + i + half);
+                    if (EPI && ep.bias) {              // materialised qkv: already rounded once, the bias add rounds again
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) {
+                            x1[e] = Elem<T>::st(__fadd_rn(Elem<T>::ld(x1[e]), Elem<T>::ld(b1[e])));
+                            x2[e] = Elem<T>::st(__fadd_rn(Elem<T>::ld(x2[e]), Elem<T>::ld(b2[e])));
+                        }
+                    }
+                }
+                if (EPI) {
+                    if (nw) {
+                        float ss = 0.f;
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) {
+                            const float u = Elem<T>::ld(x1[e]), v = Elem<T>::ld(x2[e]);
+                            ss = __fadd_rn(ss, __fmul_rn(u, u));
+                            ss = __fadd_rn(ss, __fmul_rn(v, v));
+                        }
+                        for (int m = 1; m < vph; m <<= 1) ss = __fadd_rn(ss, __shfl_xor(ss, m));
+                        const float rs = rsqrtf(__fadd_rn(__fmul_rn(ss, 1.f / d), ep.eps));
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) {
+                            x1[e] = Elem<T>::st(__fmul_rn(Elem<T>::ld(w1[e]), rnd<T>(__fmul_rn(Elem<T>::ld(x1[e]), rs))));
+                            x2[e] = Elem<T>::st(__fmul_rn(Elem<T>::ld(w2[e]), rnd<T>(__fmul_rn(Elem<T>::ld(x2[e]), rs))));
+                        }
+                    }
                 }
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
@@ -104,6 +162,35 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(typename Elem<T>::S
                 S* dst = h < H ? (q_out ? q_out + ((size_t)t * H + h) * d : x) : k_cache + ((size_t)(h - H) * S_max + P + t) * d;
                 *reinterpret_cast<uint4*>(dst + i) = *reinterpret_cast<const uint4*>(o1);
                 *reinterpret_cast<uint4*>(dst + i + half) = *reinterpret_cast<const uint4*>(o2);
+            }
+        } else if (EPI) {
+            // scalar fallback with the epilogue (materialised qkv only): one thread per head - a pass for the sum of squares, then one
+            // per pair (the pair it rewrites in place is read just before)
+            auto xin = [&](const S* x, int j, int h) {
+                float v = Elem<T>::ld(x[j]);
+                return ep.bias ? rnd<T>(__fadd_rn(v, Elem<T>::ld(ep.bias[(size_t)h * d + j]))) : v;
+            };
+            for (int h = sub * blockDim.x + threadIdx.x; h < H + Hkv; h += bpt * blockDim.x) {
+                S* x = row + (size_t)h * d;
+                const S* nw = h < H ? ep.qn : ep.kn;
+                float rs = 0.f;
+                if (nw) {
+                    float ss = 0.f;
+                    for (int j = 0; j < d; ++j) { const float u = xin(x, j, h); ss = __fadd_rn(ss, __fmul_rn(u, u)); }
+                    rs = rsqrtf(__fadd_rn(__fmul_rn(ss, 1.f / d), ep.eps));
+                }
+                S* dst = h < H ? x : k_cache + ((size_t)(h - H) * S_max + P + t) * d;
+                for (int i = 0; i < half; ++i) {
+                    float a1 = xin(x, i, h), a2 = xin(x, i + half, h);
+                    if (nw) {
+                        a1 = rnd<T>(__fmul_rn(Elem<T>::ld(nw[i]), rnd<T>(__fmul_rn(a1, rs))));
+                        a2 = rnd<T>(__fmul_rn(Elem<T>::ld(nw[i + half]), rnd<T>(__fmul_rn(a2, rs))));
+                    }
+                    const float o1 = rnd<T>(__fadd_rn(rnd<T>(__fmul_rn(a1, Elem<T>::ld(c[i]))), rnd<T>(__fmul_rn(-a2, Elem<T>::ld(s[i])))));
+                    const float o2 = rnd<T>(__fadd_rn(rnd<T>(__fmul_rn(a2, Elem<T>::ld(c[i + half]))), rnd<T>(__fmul_rn(a1, Elem<T>::ld(s[i + half])))));
+                    dst[i] = Elem<T>::st(o1);
+                    dst[i + half] = Elem<T>::st(o2);
+                }
             }
         } else {
             for (int idx = sub * blockDim.x + threadIdx.x; idx < (H + Hkv) * half; idx += bpt * blockDim.x) {
@@ -147,6 +234,10 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(typename Elem<T>::S
                 if (n_parts <= 2) sum_v(std::integral_constant<int, 2>{});
                 else if (n_parts <= 4) sum_v(std::integral_constant<int, 4>{});
                 else sum_v(std::integral_constant<int, 8>{});
+                if (EPI && ep.bias) {
+                    const S* bv = ep.bias + (size_t)(H + Hkv + kvh) * d + d0 + d4;
+                    a.x += Elem<T>::ld(bv[0]); a.y += Elem<T>::ld(bv[1]); a.z += Elem<T>::ld(bv[2]); a.w += Elem<T>::ld(bv[3]);
+                }
                 sm[tt][d4] = Elem<T>::st(a.x); sm[tt][d4 + 1] = Elem<T>::st(a.y); sm[tt][d4 + 2] = Elem<T>::st(a.z); sm[tt][d4 + 3] = Elem<T>::st(a.w);
             }
         }
@@ -158,7 +249,10 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(typename Elem<T>::S
                 if (parts) {
                     float a = 0.f;
                     for (int sp = 0; sp < n_parts; ++sp) a += parts[sp * part_stride + e0];
+                    if (EPI && ep.bias) a += Elem<T>::ld(ep.bias[(size_t)(H + Hkv + kvh) * d + d0 + dd]);
                     sm[tt][dd] = Elem<T>::st(a);
+                } else if (EPI && ep.bias) {
+                    sm[tt][dd] = Elem<T>::st(__fadd_rn(Elem<T>::ld(qkv[e0]), Elem<T>::ld(ep.bias[(size_t)(H + Hkv + kvh) * d + d0 + dd])));
                 } else {
                     sm[tt][dd] = qkv[e0];
                 }
@@ -219,15 +313,27 @@ __global__ __launch_bounds__(256) void kv_pack_bshd_kernel(const S* k, const S* 
 template <typename T>
 static int launch_rope(void* qkv, const int32_t* positions, const void* cos_tab, const void* sin_tab, void* k_cache,
                        void* vt_cache, int T_, int P, const int32_t* dyn_P, int H, int Hkv, int d, int S_max, int max_pos,
-                       hipStream_t st, const float* parts = nullptr, int n_parts = 0, size_t part_stride = 0, void* q_out = nullptr) {
+                       hipStream_t st, const float* parts = nullptr, int n_parts = 0, size_t part_stride = 0, void* q_out = nullptr,
+                       const lade_qkv_epilogue* epi = nullptr) {
     typedef typename Elem<T>::S S;
     const int n_vblk = Hkv * cdiv(T_, 64) * cdiv(d, 32);
     // one 16-byte pair item per thread: blocks per token = items / 256 (latency bound: more, smaller work-groups)
     constexpr int VEC = 16 / sizeof(S);
-    const int items = (d / 2) % VEC == 0 ? (H + Hkv) * (d / 2 / VEC) : (H + Hkv) * (d / 2);
+    const bool has_epi = epi && (epi->bias || epi->q_norm || epi->k_norm);
+    const bool norm = has_epi && (epi->q_norm || epi->k_norm);
+    const int vph = d / 2 / VEC;
+    const bool vec = (d / 2) % VEC == 0 && (!norm || (vph & (vph - 1)) == 0);          // the kernel's own choice of path
+    const int items = vec ? (H + Hkv) * vph : (has_epi ? H + Hkv : (H + Hkv) * (d / 2));
     const int bpt = std::max(1, std::min(8, cdiv(items, 256)));
-    hipLaunchKernelGGL(rope_kv_append_kernel<T>, dim3(T_ * bpt + n_vblk), dim3(256), 0, st, (S*)qkv, positions, (const S*)cos_tab,
-                       (const S*)sin_tab, (S*)k_cache, (S*)vt_cache, T_, P, dyn_P, H, Hkv, d, S_max, max_pos, parts, n_parts, part_stride, (S*)q_out, bpt);
+    const dim3 grid(T_ * bpt + n_vblk);
+    if (has_epi) {
+        const QkvEpi<S> ep{(const S*)epi->bias, (const S*)epi->q_norm, (const S*)epi->k_norm, epi->eps};
+        hipLaunchKernelGGL((rope_kv_append_kernel<T, true>), grid, dim3(256), 0, st, (S*)qkv, positions, (const S*)cos_tab, (const S*)sin_tab,
+                           (S*)k_cache, (S*)vt_cache, T_, P, dyn_P, H, Hkv, d, S_max, max_pos, parts, n_parts, part_stride, (S*)q_out, bpt, ep);
+    } else {
+        hipLaunchKernelGGL((rope_kv_append_kernel<T, false>), grid, dim3(256), 0, st, (S*)qkv, positions, (const S*)cos_tab, (const S*)sin_tab,
+                           (S*)k_cache, (S*)vt_cache, T_, P, dyn_P, H, Hkv, d, S_max, max_pos, parts, n_parts, part_stride, (S*)q_out, bpt, QkvEpi<S>{});
+    }
     return check_launch("lade_rope_kv_append");
 }
 
@@ -353,4 +459,53 @@ extern "C" int lade_rope_kv_append_parts(const float* parts, int32_t n_parts, in
         case LADE_F16: return launch_rope<F16>(nullptr, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, parts, n_parts, (size_t)part_stride, q_out);
     }
     LADE_REQUIRE(false, LADE_E_DTYPE, "lade_rope_kv_append_parts: dtype=%d", dtype);
+}
+
+// ---- the qkv epilogue (lade_qkv_epilogue): the two entry points above plus bias / per-head RMSNorm of q and k ----
+static int check_epilogue(const lade_qkv_epilogue* epi, int32_t dtype, const char* who) {
+    if (!epi || !(epi->bias || epi->q_norm || epi->k_norm)) return LADE_OK;
+    LADE_REQUIRE(((uintptr_t)epi->bias | (uintptr_t)epi->q_norm | (uintptr_t)epi->k_norm) % 16 == 0, LADE_E_ARG,
+                 "%s: bias / q_norm / k_norm must be 16-byte aligned (%p %p %p)", who, epi->bias, epi->q_norm, epi->k_norm);
+    LADE_REQUIRE(!(epi->q_norm || epi->k_norm) || (epi->eps >= 0.f && epi->eps < 1.f), LADE_E_ARG, "%s: eps=%g", who, (double)epi->eps);
+    (void)dtype;
+    return LADE_OK;
+}
+
+extern "C" int lade_rope_kv_append_ex(void* qkv, const int32_t* positions, const void* cos_tab, const void* sin_tab,
+                                      void* k_cache, void* vt_cache, int32_t T, int32_t P, const int32_t* dyn_P, int32_t H,
+                                      int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
+                                      const lade_qkv_epilogue* epi, void* stream) {
+    LADE_REQUIRE(qkv && positions && cos_tab && sin_tab && k_cache && vt_cache, LADE_E_ARG, "lade_rope_kv_append_ex: null pointer");
+    LADE_REQUIRE(T > 0 && P >= 0 && P + T <= S_max && H > 0 && Hkv > 0 && d > 0 && d % 2 == 0 && d <= 256 && max_pos > 0,
+                 LADE_E_ARG, "lade_rope_kv_append_ex: T=%d P=%d S_max=%d H=%d Hkv=%d d=%d", T, P, S_max, H, Hkv, d);
+    const int rc = check_epilogue(epi, dtype, "lade_rope_kv_append_ex");
+    if (rc != LADE_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    switch (dtype) {
+        case LADE_BF16: return launch_rope<BF16>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, nullptr, 0, 0, nullptr, epi);
+        case LADE_F16: return launch_rope<F16>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, nullptr, 0, 0, nullptr, epi);
+        case LADE_F32: return launch_rope<F32>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, nullptr, 0, 0, nullptr, epi);
+    }
+    LADE_REQUIRE(false, LADE_E_DTYPE, "lade_rope_kv_append_ex: dtype=%d", dtype);
+}
+
+extern "C" int lade_rope_kv_append_parts_ex(const float* parts, int32_t n_parts, int64_t part_stride, void* q_out, const int32_t* positions,
+                                            const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int32_t T, int32_t P,
+                                            const int32_t* dyn_P, int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
+                                            const lade_qkv_epilogue* epi, void* stream) {
+    LADE_REQUIRE(parts && q_out && positions && cos_tab && sin_tab && k_cache && vt_cache && n_parts >= 1, LADE_E_ARG, "lade_rope_kv_append_parts_ex: null pointer");
+    LADE_REQUIRE(T > 0 && P >= 0 && P + T <= S_max && H > 0 && Hkv > 0 && d > 0 && (d / 2) % 8 == 0 && d <= 256 && max_pos > 0,
+                 LADE_E_ARG, "lade_rope_kv_append_parts_ex: T=%d P=%d S_max=%d H=%d Hkv=%d d=%d", T, P, S_max, H, Hkv, d);
+    const int rc = check_epilogue(epi, dtype, "lade_rope_kv_append_parts_ex");
+    if (rc != LADE_OK) return rc;
+    // the partials are read on the 16-byte path only: the head norm's lane reduction needs the d/16 lanes of a head to be a power of two
+    const int vph = d / 16;
+    LADE_REQUIRE(!(epi && (epi->q_norm || epi->k_norm)) || (vph & (vph - 1)) == 0, LADE_E_ARG,
+                 "lade_rope_kv_append_parts_ex: the head norm needs d / 16 to be a power of two (d=%d)", d);
+    hipStream_t st = (hipStream_t)stream;
+    switch (dtype) {
+        case LADE_BF16: return launch_rope<BF16>(nullptr, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, parts, n_parts, (size_t)part_stride, q_out, epi);
+        case LADE_F16: return launch_rope<F16>(nullptr, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, parts, n_parts, (size_t)part_stride, q_out, epi);
+    }
+    LADE_REQUIRE(false, LADE_E_DTYPE, "lade_rope_kv_append_parts_ex: dtype=%d", dtype);
 }

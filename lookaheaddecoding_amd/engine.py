@@ -117,6 +117,8 @@ class StepEngine(KernelDecisions):
         self.hidden, self.inter = cfg["hidden"], cfg["inter"]
         self.L, self.H, self.Hkv, self.d, self.V = cfg["layers"], cfg["heads"], cfg["kv_heads"], cfg["head_dim"], cfg["vocab"]
         self.eps = float(cfg["eps"])
+        # Qwen2: bias on q / k / v; Qwen3: per-head RMSNorm of q and k before RoPE - both applied by the RoPE + KV append kernel (its qkv epilogue)
+        self.qkv_bias, self.qk_norm = bool(cfg.get("qkv_bias", False)), bool(cfg.get("qk_norm", False))
         self.S_max = ((max_seq + 63) // 64) * 64
         self.generation = 0                  # bumped whenever buffers are re-allocated (captured graphs become stale)
         dev, dt = self.device, dtype
@@ -150,9 +152,15 @@ class StepEngine(KernelDecisions):
                 wo=W(p + "wo", (i, "wo")).contiguous(),
                 wgu=self._fuse_gate_up(W(p + "wg"), W(p + "wu")),
                 wd=W(p + "wd", (i, "wd")).contiguous()))
+            if self.qkv_bias:                    # fused in wqkv's order: [bq | bk | bv]
+                self.layers[-1]["bqkv"] = torch.cat([W(p + "bq"), W(p + "bk"), W(p + "bv")]).contiguous()
+            if self.qk_norm:
+                self.layers[-1]["qn"], self.layers[-1]["kn"] = W(p + "qn").contiguous(), W(p + "kn").contiguous()
+        self._build_epilogues()
         # hand-written weight-streaming GEMM (split-K partials consumed by the fused glue kernels) for steps of
         # <= 256 tokens; every (N, K, row class) is timed against the library GEMM once and the faster one is kept
-        self.custom_gemm = dt != torch.float32 and os.environ.get("LADE_GEMM", "1") != "0" and self.d % 16 == 0 and self.hidden % 64 == 0 and self.inter % 64 == 0
+        self.custom_gemm = (dt != torch.float32 and os.environ.get("LADE_GEMM", "1") != "0" and self.d % 16 == 0 and self.hidden % 64 == 0
+                            and self.inter % 64 == 0 and (self.H * self.d) % 64 == 0)          # (the o projection's K is H * d, not hidden, on Qwen3)
         self.ktile, self.ktile_only, self.ktile_bytes = False, False, 0
         self._build_ktile_copies()
         self._alloc_cache(self.S_max)
@@ -202,6 +210,20 @@ class StepEngine(KernelDecisions):
                 shipped = shipped_tune_table(self.device)
                 if os.path.exists(shipped):
                     self._load_tune_file(shipped, strict=False)
+
+    @property
+    def has_epilogue(self) -> bool:
+        """the model carries a qkv epilogue (Qwen2 bias / Qwen3 head norm): RoPE + KV append is always a launch of its own"""
+        return self.qkv_bias or self.qk_norm
+
+    def _build_epilogues(self) -> None:
+        """per layer, the lade_qkv_epilogue of the two RoPE + KV append forms: `epi_parts` for the split-K path (bias and norm: the bias joins
+        the partials' sum before its one rounding), `epi_lib` after the library GEMM (norm only: torch.addmm already added the bias with
+        F.linear's one rounding).  None where nothing is left to do (the plain entry points run)."""
+        for lw in self.layers:
+            b, qn, kn = lw.get("bqkv"), lw.get("qn"), lw.get("kn")
+            lw["epi_parts"] = ops.qkv_epilogue(b, qn, kn, self.eps) if (b is not None or qn is not None) else None
+            lw["epi_lib"] = ops.qkv_epilogue(None, qn, kn, self.eps) if qn is not None else None
 
     def _fuse_gate_up(self, wg: torch.Tensor, wu: torch.Tensor) -> torch.Tensor:
         """gate and up projections as ONE weight.  16-row interleaved ([16 gate rows | their 16 up rows] per 32-row MFMA tile) so that
@@ -455,6 +477,8 @@ class StepEngine(KernelDecisions):
         # the attention launch of this row class: RoPE + KV append inside it (from the qkv GEMM's partials) or as a launch of their own,
         # the work-group shape, the split rule
         acfg = (self.attn_cfg.get(next(c for c in self.ROW_CLASSES if T <= c), self.attn_default) if fused else (0, 0, 0))
+        if self.has_epilogue and acfg[0]:           # the fused-RoPE attention forms do not carry the qkv epilogue
+            acfg = (0,) + tuple(acfg[1:])
         if n_splits is None:
             n_splits = self.n_splits_for(T, P + T, choice=acfg if fused else None)
         fuse_rope = bool(acfg[0]) and cfg_qkv is not None and cfg_qkv[2] <= 4 and not self.skip_attn
@@ -477,11 +501,21 @@ class StepEngine(KernelDecisions):
                 ops.gemm_parts(h, self._w(lw, "wqkv"), part, cfg_qkv[2], cfg_qkv[1], cfg_qkv[0], cfg_qkv[3], cfg_qkv[4], cfg_qkv[5])
                 qb = self.ws_q[:T]
                 if not fuse_rope and self.skip_attn != "all":
-                    ops.rope_kv_append_parts(part, cfg_qkv[2], qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P)
+                    if lw["epi_parts"] is not None:
+                        ops.rope_kv_append_parts_ex(part, cfg_qkv[2], qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d,
+                                                    dyn_P=dyn_P, epi=lw["epi_parts"])
+                    else:
+                        ops.rope_kv_append_parts(part, cfg_qkv[2], qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P)
                 q_in = qb
             else:
-                torch.matmul(h, self._row(lw, "wqkv").t(), out=qkv)
-                ops.rope_kv_append(qkv, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P)
+                if "bqkv" in lw:                  # F.linear with a bias: one rounding of (h W^T + b)
+                    torch.addmm(lw["bqkv"], h, self._row(lw, "wqkv").t(), out=qkv)
+                else:
+                    torch.matmul(h, self._row(lw, "wqkv").t(), out=qkv)
+                if lw["epi_lib"] is not None:
+                    ops.rope_kv_append_ex(qkv, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P, epi=lw["epi_lib"])
+                else:
+                    ops.rope_kv_append(qkv, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P)
                 q_in = qkv
             ev = None if self.skip_attn else self.attn_events      # skip_attn: `o` keeps stale values, the logits are meaningless
             if ev is not None:              # bench.py: hipEvents around the attention launch pair, in the real step

@@ -42,41 +42,69 @@ def _rope_params(c):
     return float(theta), scaling
 
 
+# the architectures the HIP step runs: class name -> (model_type, what its step adds to Llama's)
+SUPPORTED = {"LlamaForCausalLM": ("llama", None), "Qwen2ForCausalLM": ("qwen2", "qkv_bias"), "Qwen3ForCausalLM": ("qwen3", "qk_norm")}
+
+
 def config_from_hf(model) -> dict:
-    """Engine config of an HF LlamaForCausalLM.  Anything the HIP step does not implement fails loudly here - the reference
-    only patches the Llama classes (lade/utils.py:40-56), so any other architecture raises there too."""
+    """Engine config of an HF LlamaForCausalLM, Qwen2ForCausalLM (q / k / v bias) or Qwen3ForCausalLM (per-head q / k RMSNorm).  Anything the
+    HIP step does not implement fails loudly here - the reference only patches the Llama classes (lade/utils.py:40-56), so any other
+    architecture raises there too."""
     c = model.config
-    if type(model).__name__ != "LlamaForCausalLM" or getattr(c, "model_type", "llama") != "llama":
-        raise cabi.LadeHipError(f"lookahead decoding supports LlamaForCausalLM only (got {type(model).__name__}, model_type="
+    cls = type(model).__name__
+    mtype, extra = SUPPORTED.get(cls, (None, None))
+    if mtype is None or getattr(c, "model_type", mtype) != mtype:
+        raise cabi.LadeHipError(f"lookahead decoding supports {', '.join(SUPPORTED)} only (got {cls}, model_type="
                                 f"{getattr(c, 'model_type', None)!r}); the reference patches the Llama classes only (lade/utils.py:40-56)")
+    if mtype != "llama":
+        # sliding-window layers need a windowed attention mask the HIP attention kernel does not implement
+        if getattr(c, "use_sliding_window", False) or "sliding_attention" in (getattr(c, "layer_types", None) or ()):
+            raise cabi.LadeHipError(f"{cls}: sliding-window attention is not supported (use_sliding_window / layer_types)")
+        if mtype == "qwen3" and getattr(c, "attention_bias", False):
+            raise cabi.LadeHipError(f"{cls}: attention_bias=True also biases o_proj, which the HIP step does not implement")
+        if getattr(c, "mlp_bias", False):
+            raise cabi.LadeHipError(f"{cls}: mlp_bias is not supported")
     theta, scaling = _rope_params(c)
     if scaling is not None:
         kind = scaling.get("rope_type", scaling.get("type"))
         if kind not in ("linear", "llama3", "dynamic"):
             # ('dynamic' = LlamaDynamicNTKScalingRotaryEmbedding, lade/models/modeling_llama.py:292-318: per-step rows, engine._ntk_rows)
             raise cabi.LadeHipError(f"rope_scaling type {kind!r} is not implemented by the HIP step (default, linear, dynamic and llama3 are)")
-    if getattr(c, "attention_bias", False) or getattr(c, "mlp_bias", False):
+    if mtype == "llama" and (getattr(c, "attention_bias", False) or getattr(c, "mlp_bias", False)):
         raise cabi.LadeHipError("projection biases are not supported (Llama-2 has none)")
     if getattr(c, "pretraining_tp", 1) not in (None, 1):
         raise cabi.LadeHipError("pretraining_tp > 1 is out of scope (DESIGN.md section 8)")
     heads = c.num_attention_heads
     head_dim = getattr(c, "head_dim", None) or c.hidden_size // heads
-    return dict(hidden=c.hidden_size, inter=c.intermediate_size, layers=c.num_hidden_layers, heads=heads,
-                kv_heads=getattr(c, "num_key_value_heads", heads) or heads, head_dim=head_dim, vocab=c.vocab_size,
-                eps=float(c.rms_norm_eps), rope_theta=theta, rope_scaling=scaling,
-                max_pos=int(getattr(c, "max_position_embeddings", 4096)))
+    cfg = dict(hidden=c.hidden_size, inter=c.intermediate_size, layers=c.num_hidden_layers, heads=heads,
+               kv_heads=getattr(c, "num_key_value_heads", heads) or heads, head_dim=head_dim, vocab=c.vocab_size,
+               eps=float(c.rms_norm_eps), rope_theta=theta, rope_scaling=scaling,
+               max_pos=int(getattr(c, "max_position_embeddings", 4096)))
+    if extra is not None:
+        cfg[extra] = True
+        cfg["tied"] = bool(getattr(c, "tie_word_embeddings", False))
+    return cfg
 
 
 def weights_from_hf(model) -> dict:
-    """References (no copies) to the HF module's parameters in the engine's naming."""
+    """References (no copies) to the HF module's parameters in the engine's naming (Qwen2: + bq / bk / bv, Qwen3: + qn / kn)."""
     m = model.model
+    extra = SUPPORTED.get(type(model).__name__, (None, None))[1]
     w = {"embed": m.embed_tokens.weight.data, "norm": m.norm.weight.data, "lm_head": model.lm_head.weight.data}
     for i, layer in enumerate(m.layers):
         a, mlp = layer.self_attn, layer.mlp
+        biased = (a.q_proj, a.k_proj, a.v_proj) if extra == "qkv_bias" else ()
         for bias_owner in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, mlp.gate_proj, mlp.up_proj, mlp.down_proj):
-            if getattr(bias_owner, "bias", None) is not None:
-                raise cabi.LadeHipError("projection biases are not supported (Llama has none)")
+            if getattr(bias_owner, "bias", None) is not None and bias_owner not in biased:
+                raise cabi.LadeHipError("projection biases are not supported (Llama has none; Qwen2 biases q / k / v only)")
         p = f"layers.{i}."
+        if extra == "qkv_bias":
+            for key, proj in (("bq", a.q_proj), ("bk", a.k_proj), ("bv", a.v_proj)):
+                if proj.bias is None:
+                    raise cabi.LadeHipError(f"{type(model).__name__}: {key} is missing (Qwen2 biases q / k / v)")
+                w[p + key] = proj.bias.data
+        elif extra == "qk_norm":
+            w[p + "qn"], w[p + "kn"] = a.q_norm.weight.data, a.k_norm.weight.data
         w.update({p + "ln1": layer.input_layernorm.weight.data, p + "ln2": layer.post_attention_layernorm.weight.data,
                   p + "wq": a.q_proj.weight.data, p + "wk": a.k_proj.weight.data, p + "wv": a.v_proj.weight.data,
                   p + "wo": a.o_proj.weight.data, p + "wg": mlp.gate_proj.weight.data, p + "wu": mlp.up_proj.weight.data,

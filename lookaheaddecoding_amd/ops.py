@@ -211,6 +211,31 @@ def rope_kv_append(qkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor
          d, k_cache.shape[1], cos.shape[0], dtype_code(qkv))
 
 
+def qkv_epilogue(bias: Optional[torch.Tensor] = None, q_norm: Optional[torch.Tensor] = None, k_norm: Optional[torch.Tensor] = None,
+                 eps: float = 1e-6) -> cabi.QkvEpilogue:
+    """lade_qkv_epilogue over device tensors in the model dtype: bias [(H+2Hkv)*d] (Qwen2's q / k / v bias, fused like wqkv), q_norm / k_norm [d]
+    (Qwen3's per-head RMSNorm weights).  The struct holds raw pointers: the tensors must outlive every launch (and every captured graph) that
+    uses it."""
+    for name, t in (("bias", bias), ("q_norm", q_norm), ("k_norm", k_norm)):
+        if t is not None:
+            _dev(t, name)
+            assert t.dim() == 1 and t.is_contiguous(), f"{name} must be a contiguous vector"
+    return cabi.QkvEpilogue(ptr(bias), ptr(q_norm), ptr(k_norm), float(eps))
+
+
+def rope_kv_append_ex(qkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
+                      vt_cache: torch.Tensor, P: int, *, H: int, Hkv: int, d: int, dyn_P: Optional[torch.Tensor] = None,
+                      epi: Optional[cabi.QkvEpilogue] = None) -> None:
+    """rope_kv_append with the qkv epilogue (`qkv_epilogue`; None = the plain kernel)."""
+    _dev(qkv, "qkv")
+    T = qkv.shape[0]
+    assert qkv.is_contiguous() and qkv.shape[1] == (H + 2 * Hkv) * d
+    assert positions.dtype == torch.int32 and positions.numel() >= T
+    assert cos.dtype == qkv.dtype and cos.shape[1] == d and cos.is_contiguous() and sin.is_contiguous()
+    call("lade_rope_kv_append_ex", ptr(qkv), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache), ptr(vt_cache), T, P, ptr(dyn_P), H, Hkv,
+         d, k_cache.shape[1], cos.shape[0], dtype_code(qkv), None if epi is None else C.byref(epi))
+
+
 def kv_commit(cache: torch.Tensor, src: int, dst: int, cnt: int, ctl: Optional[torch.Tensor] = None) -> None:
     """cache [L, 2, Hkv*S_max*d] viewed as K [Hkv,S_max,d] / V^T [Hkv,d,S_max] per layer."""
     L = cache.shape[0]
@@ -449,3 +474,11 @@ def rope_kv_append_parts(part: torch.Tensor, n_parts: int, q_out: torch.Tensor, 
                          dyn_P: Optional[torch.Tensor] = None) -> None:
     call("lade_rope_kv_append_parts", ptr(part), n_parts, T * (H + 2 * Hkv) * d, ptr(q_out), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache),
          ptr(vt_cache), T, P, ptr(dyn_P), H, Hkv, d, k_cache.shape[1], cos.shape[0], dtype_code(q_out))
+
+
+def rope_kv_append_parts_ex(part: torch.Tensor, n_parts: int, q_out: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                            k_cache: torch.Tensor, vt_cache: torch.Tensor, T: int, P: int, *, H: int, Hkv: int, d: int,
+                            dyn_P: Optional[torch.Tensor] = None, epi: Optional[cabi.QkvEpilogue] = None) -> None:
+    """rope_kv_append_parts with the qkv epilogue: the bias joins the fp32 sum of the partials before its one rounding"""
+    call("lade_rope_kv_append_parts_ex", ptr(part), n_parts, T * (H + 2 * Hkv) * d, ptr(q_out), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache),
+         ptr(vt_cache), T, P, ptr(dyn_P), H, Hkv, d, k_cache.shape[1], cos.shape[0], dtype_code(q_out), None if epi is None else C.byref(epi))

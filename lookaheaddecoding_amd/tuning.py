@@ -78,8 +78,11 @@ class KernelDecisions:
         """what a persisted decision table is valid for: the model shape, the dtype, the weight layouts the kernels stream, the GPU and the probe
         context - NOT this engine's buffer sizes (S_max, max_T): two differently sized engines of one model share a table (the in-step probe
         runs at a fixed context; an engine whose cache is smaller than it has its own key, as it has its own in-process decision)"""
-        return json.dumps([self.hidden, self.inter, self.H, self.Hkv, self.d, self.L, self.V, str(self.dtype), list(self.kt_names), self.gu_layout,
-                           bool(self.ktile_only), min(self.STEP_TUNE_CONTEXT, self.S_max), self._step_tunable()])
+        key = [self.hidden, self.inter, self.H, self.Hkv, self.d, self.L, self.V, str(self.dtype), list(self.kt_names), self.gu_layout,
+               bool(self.ktile_only), min(self.STEP_TUNE_CONTEXT, self.S_max), self._step_tunable()]
+        if self.has_epilogue:                # (Llama keys stay as they were: the shipped table matches them byte for byte)
+            key.append("qkv_epi:" + "+".join(n for n, on in (("bias", self.qkv_bias), ("qk_norm", self.qk_norm)) if on))
+        return json.dumps(key)
 
     def _tune_header(self) -> dict:
         return {"version": self.TUNE_FILE_VERSION, "abi": cabi.ABI_VERSION, "device": gpu_identity(self.device)[0], "n_cu": self.n_cu,
@@ -403,7 +406,7 @@ class KernelDecisions:
         ctx = min(self.STEP_TUNE_CONTEXT, self.S_max)
         skey = (self.hidden, self.inter, self.H, self.Hkv, self.d, self.L, mclass, str(self.dtype), torch.cuda.get_device_name(self.device),
                 self.n_cu, tuple(self.kt_names), self.gu_layout, tuple(self.gemm_cfg[(n, mclass)] for n in self.LAYER_GEMMS), ctx, self.attn_default,
-                cabi.debug("attn_tune", "0"))
+                cabi.debug("attn_tune", "0"), self.qkv_bias, self.qk_norm)
         with _STEP_TUNE_LOCK:
             if skey not in _STEP_TUNE_CACHE:
                 _STEP_TUNE_CACHE[skey] = self._refine_timed(mclass, T, n_probe, ctx)
@@ -474,7 +477,7 @@ class KernelDecisions:
         if cabi.debug("attn_tune", "0") != "1":
             return [inc]
         qkv = self.gemm_cfg.get(("wqkv", mclass))
-        fused_ok = (cabi.experimental() and qkv is not None and qkv[3] >= 0 and qkv[2] <= 4 and cabi.debug("fuse_rope", "") not in ("", "off"))
+        fused_ok = (cabi.experimental() and not self.has_epilogue and qkv is not None and qkv[3] >= 0 and qkv[2] <= 4 and cabi.debug("fuse_rope", "") not in ("", "off"))
         fuses = (1, 0) if fused_ok else (0,)          # (the producer mode, fused = 2, only ever by LADE_DEBUG=fuse_rope=2 as the default: never picked by a tuner)
         rows = (self.H // self.Hkv) * T
         shapes = [128, 64] + ([32] if rows <= 64 or self.H != self.Hkv else [])
