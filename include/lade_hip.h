@@ -50,6 +50,8 @@
  *   lade_rope_kv_append_ex / lade_rope_kv_append_parts_ex   the two RoPE + KV append entry points with the qkv epilogue of
  *                            Qwen2 (q / k / v bias) and Qwen3 (per-head RMSNorm of q and k before RoPE); the reference adapts
  *                            Llama only
+ *   lade_gen_ctl_init / lade_gen_ctl_update / lade_gen_argmax / lade_gen_rows / lade_greedy_post_step_ex   HF's repetition penalty,
+ *                            min-length processors and EOS sets on the step's rows (the reference refuses them, lade/decoding.py:968)
  *   lade_time_attn / lade_time_attn_rot   hipEvent timing helpers for bench.py (no reference counterpart)
  */
 #ifndef LADE_HIP_H
@@ -62,7 +64,8 @@ extern "C" {
 #endif
 
 #define LADE_ABI_VERSION 3      /* 2: lade_attn_args grew (wg_rows, fused RoPE), lade_gemm_skinny* take `ring`, lade_greedy_post_step takes record_host;
-                                 * 3: + lade_gemm_ra_kt, lade_build_flags (nothing that existed changed) */
+                                 * 3: + lade_gemm_ra_kt, lade_build_flags; + lade_gen_ctl_init, lade_gen_ctl_update, lade_gen_argmax,
+                                 *    lade_gen_rows, lade_greedy_post_step_ex (nothing that existed changed) */
 
 /* error codes */
 #define LADE_OK 0
@@ -289,6 +292,59 @@ int lade_greedy_post_step(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* 
                           int32_t* guess, int32_t T_step, int32_t cand_rows, int32_t phase, int32_t pool_from_prompt,
                           int32_t* tail, int32_t eos, const int32_t* forced, const int32_t* level_override,
                           int32_t* record, int32_t* record_host, void* stream);
+
+/* The same with a SET of end-of-sequence ids: eos_set = host array of n_eos ids (0..LADE_GEN_MAX_EOS, each >= 0), copied into the
+ * launch.  The EOS scan stops at the first accepted token that is in the set; the tokens accepted after it in the same step are
+ * dropped.  lade_greedy_post_step(..., eos, ...) launches the same kernel with the set {eos} (empty when eos < 0). */
+int lade_greedy_post_step_ex(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* pool_tok, int32_t* pool_cnt,
+                             int32_t V, int32_t W, int32_t N, int32_t G, const int32_t* am, int32_t n_inp,
+                             int32_t* guess, int32_t T_step, int32_t cand_rows, int32_t phase, int32_t pool_from_prompt,
+                             int32_t* tail, const int32_t* eos_set, int32_t n_eos, const int32_t* forced,
+                             const int32_t* level_override, int32_t* record, int32_t* record_host, void* stream);
+
+/* ---- generation controls (HF's RepetitionPenaltyLogitsProcessor, MinLengthLogitsProcessor / MinNewTokensLengthLogitsProcessor) ----
+ * The controls of one sequence live in a device block of int32 words `gen` (LADE_GEN_WORDS(V)), never in kernel arguments: a captured
+ * step reads them at replay, so a new prompt (new seen set, new min_len) needs no re-capture.
+ *   gen[LADE_GEN_PENALTY]      penalty p as fp32 bits (1.0 = off)
+ *   gen[LADE_GEN_INV_PENALTY]  fp32 bits of (float)(1.0 / p), the reciprocal taken in double: torch's device kernel divides by a
+ *                              scalar as a multiplication by that reciprocal, so HF's s / p is s * inv here (bit-exact against torch)
+ *   gen[LADE_GEN_MIN_LEN]      absolute minimum length (min_length, or prompt length + min_new_tokens; 0 = off)
+ *   gen[LADE_GEN_N_EOS], gen[LADE_GEN_EOS + e]   the ids masked to -inf while a row's sequence length L < min_len
+ *   gen[LADE_GEN_VOCAB]        V
+ *   gen[LADE_GEN_SEEN ..]      seen-set bitmap, ceil(V/32) words: bit t = token t occurs in prompt + accepted tokens */
+#define LADE_GEN_MAX_EOS 8
+#define LADE_GEN_PENALTY 0
+#define LADE_GEN_INV_PENALTY 1
+#define LADE_GEN_MIN_LEN 2
+#define LADE_GEN_N_EOS 3
+#define LADE_GEN_VOCAB 4
+#define LADE_GEN_EOS 8
+#define LADE_GEN_SEEN 16
+#define LADE_GEN_WORDS(V) (LADE_GEN_SEEN + ((V) + 31) / 32)
+#define LADE_GEN_MAX_VOCAB (1 << 18)    /* a row's penalised set is staged in LDS: <= 32 KiB */
+
+/* Writes the block: penalty (> 0, double: the value HF holds) / min_len (>= 0) / the min-length EOS ids (host array, n_eos <= LADE_GEN_MAX_EOS), and the seen set =
+ * the n_prompt prompt tokens (device).  Once per sequence, before its first step. */
+int lade_gen_ctl_init(int32_t* gen, int32_t V, double penalty, int32_t min_len, const int32_t* eos_ids, int32_t n_eos,
+                      const int32_t* prompt, int32_t n_prompt, void* stream);
+/* Adds the tokens the last post-step accepted (ctl[LADE_CTL_HITS ..], ctl[LADE_CTL_N_ACCEPT] of them) to the seen set: after every
+ * post-step, inside a captured step too (no host round trip). */
+int lade_gen_ctl_update(int32_t* gen, const int32_t* ctl, void* stream);
+/* Row argmax of one step under the controls.  logits [rows][ld] (model dtype), rows = [out row | n_inp window rows | candidate rows, gs
+ * positions each]; candidate slots c >= ctl[LADE_CTL_G] are padding (am = 0, nothing else written).  Row r predicts the token at sequence
+ * length L = pos[sel ? sel[r] : r] + 1 (pos / sel: the step's position ids and row selection, device).  Penalised set: the seen set,
+ * plus guess[c][0..j] for position j of candidate c; window rows use the seen set alone (they feed the window and the pool, never an
+ * emitted token).  Per row in fp32: s -> s < 0 ? s * p : s * inv once per distinct token of the set, then -inf for the EOS ids when
+ * L < min_len; am[r] = the argmax in torch.argmax's order.  One pass over the logits, no fp32 copy. */
+int lade_gen_argmax(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t dtype, int32_t n_inp, int32_t gs,
+                    const int32_t* gen, const int32_t* ctl, const int32_t* guess, const int32_t* pos, const int32_t* sel,
+                    int32_t* am, void* stream);
+/* The same, plus the processed fp32 rows of the out row and the candidate rows: rows_out[0] = out row, rows_out[1 + c*gs + j] =
+ * position j of candidate c (row stride V; padded candidate slots are not written) - what lade_softmax_gather / lade_warp_rows read
+ * with dtype LADE_F32 and skip = 0 (sampling). */
+int lade_gen_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t dtype, int32_t n_inp, int32_t gs,
+                  const int32_t* gen, const int32_t* ctl, const int32_t* guess, const int32_t* pos, const int32_t* sel,
+                  int32_t* am, float* rows_out, void* stream);
 
 /* lookahead parallelism: record packing, then (after the all-gather of rec_words int32 per rank, lade_lp_allgather
  * or the host's collective) the deterministic reduction every rank applies (same phases as above).

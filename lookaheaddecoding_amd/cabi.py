@@ -27,6 +27,13 @@ CTL_KV_SRC, CTL_KV_DST, CTL_KV_CNT, CTL_FIRST_GUESS = 10, 11, 12, 13
 CTL_HITS, CTL_WLEN, CTL_WORDS = 16, 32, 64
 MAX_LEVEL, MAX_WINDOW, MAX_GUESS_SET = 16, 128, 64
 REC_WORDS = 8 + MAX_LEVEL
+# generation-control block (include/lade_hip.h: LADE_GEN_*)
+GEN_MAX_EOS, GEN_SEEN, GEN_MAX_VOCAB = 8, 16, 1 << 18
+
+
+def gen_words(V: int) -> int:
+    """int32 words of the generation-control block of a vocabulary of V (LADE_GEN_WORDS)"""
+    return GEN_SEEN + (V + 31) // 32
 
 
 def record_seal(rec, step_no: int) -> int:
@@ -87,6 +94,12 @@ SIGNATURES = {
     "lade_window_roll": [_vp, _i32, _vp, _vp, _i32, _i32, _vp],
     "lade_greedy_post_step": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp,
                               _i32, _vp, _vp, _vp, _vp, _vp],
+    "lade_greedy_post_step_ex": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp,
+                                 _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "lade_gen_ctl_init": [_vp, _i32, C.c_double, _i32, _vp, _i32, _vp, _i32, _vp],
+    "lade_gen_ctl_update": [_vp, _vp, _vp],
+    "lade_gen_argmax": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lade_gen_rows": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lade_lp_pack": [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp],
     "lade_lp_reduce_apply": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp],
     "lade_lp_unique_id": [_vp],

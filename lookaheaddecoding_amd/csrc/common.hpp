@@ -25,6 +25,17 @@ int debug_int(const char* name);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// a set of up to LADE_GEN_MAX_EOS end-of-sequence ids, passed by value into a launch (n = 0: no EOS)
+struct EosIds {
+    int32_t n;
+    int32_t id[LADE_GEN_MAX_EOS];
+    __host__ __device__ bool has(int32_t t) const {
+        bool in = false;
+        for (int e = 0; e < n; ++e) in |= id[e] == t;
+        return in;
+    }
+};
+
 // seal of a step record (include/lade_hip.h: lade_record_seal): one definition for the kernel that writes it and the host that checks it
 __host__ __device__ static inline uint32_t seal_words(const uint32_t* rec, uint32_t step_no) {
     uint32_t x = step_no * 0x9E3779B1u + 0x7F4A7C15u;

@@ -373,14 +373,14 @@ __global__ __launch_bounds__(64) void argmax_pairs_kernel(const float2* pairs, i
 // (which, in the greedy path, receives hits[max_hit] once per accepted index: decoding.py:1175).
 
 // EOS scan + POOL_FROM_PROMPT appends (lade/decoding.py:1167-1177); returns n_accept, sets *finished
-__device__ int accept_scan(const int32_t* hits, int max_hit, int eos, int pool_from_prompt, int32_t* tail, int32_t* ng,
+__device__ int accept_scan(const int32_t* hits, int max_hit, const EosIds& eos, int pool_from_prompt, int32_t* tail, int32_t* ng,
                            int32_t* pool_tok, int32_t* pool_cnt, int V, int G, int N, int sample_mode, int* finished) {
     const int lane = threadIdx.x;
     const int gs = N - 1;
     int n_accept = max_hit + 1;
     *finished = 0;
     for (int hit_idx = 0; hit_idx <= max_hit; ++hit_idx) {
-        if (eos >= 0 && hits[hit_idx] == eos) { n_accept = hit_idx + 1; *finished = 1; break; }
+        if (eos.has(hits[hit_idx])) { n_accept = hit_idx + 1; *finished = 1; break; }
         // greedy appends hits[max_hit] for every accepted index (decoding.py:1175), sampling hits[hit_idx] (:601)
         const int new_lst = sample_mode ? hits[hit_idx] : hits[max_hit];
         if (pool_from_prompt) {
@@ -407,7 +407,7 @@ __device__ int accept_scan(const int32_t* hits, int max_hit, int eos, int pool_f
 __global__ __launch_bounds__(64) void greedy_post_step_kernel(int32_t* ctl, int32_t* window, int wcap, int32_t* pool_tok,
                                                               int32_t* pool_cnt, int V, int W, int N, int G, const int32_t* am,
                                                               int n_inp, int32_t* guess, int T_step, int cand_rows, int phase,
-                                                              int pool_from_prompt, int32_t* tail, int eos, const int32_t* forced,
+                                                              int pool_from_prompt, int32_t* tail, EosIds eos, const int32_t* forced,
                                                               const int32_t* level_override, int32_t* record, int32_t* record_host) {
     __shared__ int32_t tup[LADE_MAX_LEVEL];
     __shared__ int32_t hits[LADE_MAX_LEVEL];
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(64) void lp_pack_kernel(const int32_t* am_out, cons
 __global__ __launch_bounds__(64) void lp_reduce_apply_kernel(const int32_t* all_rec, int R, int rec_words, int split, int32_t* ctl,
                                                              int32_t* window, int wcap, int32_t* pool_tok, int32_t* pool_cnt, int V,
                                                              int W, int N, int G, int phase, int32_t* guess_all, int32_t* scratch,
-                                                             int32_t* record, int pool_from_prompt, int32_t* tail, int eos) {
+                                                             int32_t* record, int pool_from_prompt, int32_t* tail, EosIds eos) {
     __shared__ int32_t tup[LADE_MAX_LEVEL];
     __shared__ int32_t hits[LADE_MAX_LEVEL];
     __shared__ int32_t ng[LADE_MAX_LEVEL + 1];
@@ -714,19 +714,51 @@ extern "C" int lade_argmax_pairs(const float* pairs, int32_t rows, int32_t n_blo
 
 extern "C" uint32_t lade_record_seal(const uint32_t* rec, uint32_t step_no) { return rec ? seal_words(rec, step_no) : 0u; }
 
+// EOS ids of the single-id entry points (eos < 0: none) as the set the kernels test
+static EosIds eos_one(int32_t eos) {
+    EosIds e = {};
+    e.n = eos >= 0 ? 1 : 0;
+    e.id[0] = eos;
+    return e;
+}
+
+#define POST_STEP_ARGS_OK(fn)                                                                                                              \
+    POOL_ARGS_OK(fn);                                                                                                                      \
+    LADE_REQUIRE(ctl && window && am && guess && record && W > 0 && W + N - 3 <= wcap && N >= 3 && N <= LADE_MAX_LEVEL && T_step > 0 &&   \
+                     cand_rows >= 0 && phase >= 0 && phase <= 2 && n_inp > 0 && n_inp <= wcap && (phase != 2 || n_inp == W),             \
+                 LADE_E_ARG, fn ": W=%d N=%d wcap=%d T=%d phase=%d n_inp=%d", W, N, wcap, T_step, phase, n_inp);                           \
+    LADE_REQUIRE(!pool_from_prompt || tail, LADE_E_ARG, fn ": POOL_FROM_PROMPT needs the tail buffer")
+
 extern "C" int lade_greedy_post_step(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* pool_tok, int32_t* pool_cnt, int32_t V,
                                      int32_t W, int32_t N, int32_t G, const int32_t* am, int32_t n_inp, int32_t* guess, int32_t T_step,
                                      int32_t cand_rows, int32_t phase, int32_t pool_from_prompt, int32_t* tail, int32_t eos,
                                      const int32_t* forced, const int32_t* level_override, int32_t* record, int32_t* record_host, void* stream) {
     const int gs = N - 1;
-    POOL_ARGS_OK("lade_greedy_post_step");
-    LADE_REQUIRE(ctl && window && am && guess && record && W > 0 && W + N - 3 <= wcap && N >= 3 && N <= LADE_MAX_LEVEL && T_step > 0 && cand_rows >= 0 &&
-                     phase >= 0 && phase <= 2 && n_inp > 0 && n_inp <= wcap && (phase != 2 || n_inp == W),
-                 LADE_E_ARG, "lade_greedy_post_step: W=%d N=%d wcap=%d T=%d phase=%d n_inp=%d", W, N, wcap, T_step, phase, n_inp);
-    LADE_REQUIRE(!pool_from_prompt || tail, LADE_E_ARG, "lade_greedy_post_step: POOL_FROM_PROMPT needs the tail buffer");
+    POST_STEP_ARGS_OK("lade_greedy_post_step");
+    // = lade_greedy_post_step_ex with a set of one id (none when eos < 0)
+    hipLaunchKernelGGL(greedy_post_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ctl, window, wcap, pool_tok, pool_cnt, V, W, N, G,
+                       am, n_inp, guess, T_step, cand_rows, phase, pool_from_prompt, tail, eos_one(eos), forced, level_override, record, record_host);
+    return check_launch("lade_greedy_post_step");
+}
+
+extern "C" int lade_greedy_post_step_ex(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* pool_tok, int32_t* pool_cnt, int32_t V,
+                                        int32_t W, int32_t N, int32_t G, const int32_t* am, int32_t n_inp, int32_t* guess, int32_t T_step,
+                                        int32_t cand_rows, int32_t phase, int32_t pool_from_prompt, int32_t* tail, const int32_t* eos_set,
+                                        int32_t n_eos, const int32_t* forced, const int32_t* level_override, int32_t* record,
+                                        int32_t* record_host, void* stream) {
+    const int gs = N - 1;
+    POST_STEP_ARGS_OK("lade_greedy_post_step_ex");
+    LADE_REQUIRE(n_eos >= 0 && n_eos <= LADE_GEN_MAX_EOS && (n_eos == 0 || eos_set), LADE_E_ARG,
+                 "lade_greedy_post_step_ex: n_eos=%d (0..%d, eos_set needed when > 0)", n_eos, LADE_GEN_MAX_EOS);
+    EosIds eos = {};
+    eos.n = n_eos;
+    for (int e = 0; e < n_eos; ++e) {
+        LADE_REQUIRE(eos_set[e] >= 0, LADE_E_ARG, "lade_greedy_post_step_ex: eos_set[%d]=%d is negative", e, eos_set[e]);
+        eos.id[e] = eos_set[e];
+    }
     hipLaunchKernelGGL(greedy_post_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ctl, window, wcap, pool_tok, pool_cnt, V, W, N, G,
                        am, n_inp, guess, T_step, cand_rows, phase, pool_from_prompt, tail, eos, forced, level_override, record, record_host);
-    return check_launch("lade_greedy_post_step");
+    return check_launch("lade_greedy_post_step_ex");
 }
 
 extern "C" int lade_lp_pack(const int32_t* am_out, const int32_t* am_inp, int32_t n_inp, const int32_t* am_guess, int32_t g_local,
@@ -751,6 +783,6 @@ extern "C" int lade_lp_reduce_apply(const int32_t* all_rec, int32_t R, int32_t r
     LADE_REQUIRE(all_rec && ctl && window && guess_all && scratch && record && R > 0 && rec_words >= 4 + split && W <= wcap && N >= 3 && N <= LADE_MAX_LEVEL,
                  LADE_E_ARG, "lade_lp_reduce_apply: R=%d rec_words=%d split=%d", R, rec_words, split);
     hipLaunchKernelGGL(lp_reduce_apply_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, all_rec, R, rec_words, split, ctl, window, wcap,
-                       pool_tok, pool_cnt, V, W, N, G, phase, guess_all, scratch, record, pool_from_prompt, tail, eos);
+                       pool_tok, pool_cnt, V, W, N, G, phase, guess_all, scratch, record, pool_from_prompt, tail, eos_one(eos));
     return check_launch("lade_lp_reduce_apply");
 }

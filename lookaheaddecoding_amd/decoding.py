@@ -29,6 +29,39 @@ CONFIG_MAP: dict = {}
 COLOR_PRINT = int(os.environ.get("COLOR_PRINT", 0))
 
 
+@dataclass(frozen=True)
+class GenControls:
+    """HF's RepetitionPenaltyLogitsProcessor and min-length family as the device step applies them (include/lade_hip.h, "generation
+    controls").  penalty: HF's `repetition_penalty` (1.0 = off).  min_len: absolute minimum sequence length, `min_length` or prompt length
+    + `min_new_tokens` (0 = off).  min_len_eos: the ids masked while a row is shorter than min_len (None: the stopping EOS set)."""
+    penalty: float = 1.0
+    min_len: int = 0
+    min_len_eos: Optional[tuple] = None
+
+    @property
+    def active(self) -> bool:
+        return self.penalty != 1.0 or self.min_len > 0
+
+
+def eos_set(eos_token_id) -> tuple:
+    """EOS ids as a tuple in first-seen order: None -> (), an int, a sequence or a tensor of ints -> their distinct non-negative ids
+    (at most cabi.GEN_MAX_EOS)"""
+    if eos_token_id is None:
+        return ()
+    if hasattr(eos_token_id, "tolist"):
+        eos_token_id = eos_token_id.tolist()
+    if isinstance(eos_token_id, (list, tuple)):
+        ids = []
+        for t in eos_token_id:
+            if t is not None and int(t) >= 0 and int(t) not in ids:
+                ids.append(int(t))
+    else:
+        ids = [int(eos_token_id)] if int(eos_token_id) >= 0 else []
+    if len(ids) > cabi.GEN_MAX_EOS:
+        raise cabi.LadeHipError(f"{len(ids)} EOS ids: the device step takes at most {cabi.GEN_MAX_EOS}")
+    return tuple(ids)
+
+
 @dataclass
 class GenOut:
     tokens: List[int]            # prompt + generated, trimmed to max_length like the reference (:1221-1229)
@@ -166,7 +199,10 @@ class LookaheadDecoder:
     # ---- stepwise API (bench.py drives single steps; greedy() is start + step until done) ----------
     @torch.no_grad()
     @_on_device
-    def start(self, prompt: Sequence[int], eos_token_id: Optional[int] = None, rng: Optional[random.Random] = None) -> None:
+    def start(self, prompt: Sequence[int], eos_token_id=None, rng: Optional[random.Random] = None,
+              controls: Optional[GenControls] = None) -> None:
+        """eos_token_id: an int, a sequence of ints or None.  controls: GenControls (repetition penalty / min length) or None; with None
+        and at most one EOS id a step launches exactly the kernels of the plain step."""
         e, st = self.e, self.st
         W, N, G, gs = self.W, self.N, self.G, self.gs
         rng = rng if rng is not None else random
@@ -178,11 +214,42 @@ class LookaheadDecoder:
         if self.pool_from_prompt:                                   # :915-916
             pt = torch.tensor(self.prompt, dtype=torch.int32, device=e.device)
             call("lade_pool_fill_prompt", ptr(st.pool_tok), ptr(st.pool_cnt), st.V, G, gs, ptr(pt), len(self.prompt))
-        self.eos = -1 if eos_token_id is None else int(eos_token_id)
+        self.eos_set = eos_set(eos_token_id)
+        self.eos = self.eos_set[0] if self.eos_set else -1
+        self.controls = controls if controls is not None and controls.active else None
+        if self.controls is not None:
+            if getattr(self, "_gen", None) is None:
+                self._gen = torch.zeros(cabi.gen_words(st.V), dtype=torch.int32, device=e.device)
+            c = self.controls
+            mask_eos = self.eos_set if c.min_len_eos is None else eos_set(c.min_len_eos)
+            ops.gen_ctl_init(self._gen, st.V, c.penalty, c.min_len if mask_eos else 0, mask_eos,
+                             torch.tensor(self.prompt, dtype=torch.int32, device=e.device))
         self.tokens = list(self.prompt)
         self.steps, self.P, self.g, self.fill_level = 0, 0, 0, 0
         self._step_no = 0                  # st.reset zeroed ctl[STEP]
         self.finished_by_eos = False
+
+    def _post_step(self, am, n_inp: int, T: int, cand_rows: int, phase: int, forced=None, level_override=None, record_host=None) -> None:
+        """The fused post-step (+ the seen-set update under controls).  At most one EOS id and no controls: lade_greedy_post_step, the
+        plain step's launch; otherwise lade_greedy_post_step_ex with the whole EOS set."""
+        e, st = self.e, self.st
+        head = (ptr(st.ctl), ptr(st.window), st.wcap, ptr(st.pool_tok), ptr(st.pool_cnt), st.V, self.W, self.N, self.G, ptr(am), n_inp,
+                ptr(st.guess), T, cand_rows, phase, int(self.pool_from_prompt), ptr(st.tail))
+        tail = (ptr(forced), ptr(level_override), ptr(st.record), ptr(record_host))
+        if self.controls is None and len(self.eos_set) <= 1:
+            call("lade_greedy_post_step", *head, self.eos, *tail)
+        else:
+            call("lade_greedy_post_step_ex", *head, ops.host_ids(self.eos_set), len(self.eos_set), *tail)
+        if self.controls is not None:
+            ops.gen_ctl_update(self._gen, st.ctl)
+
+    def _gen_rows(self, logits: torch.Tensor, n_inp: int, pos: torch.Tensor, sel: Optional[torch.Tensor], rows_out=None) -> None:
+        """processed argmax of a step's rows into st.am (and the processed fp32 out / candidate rows into rows_out)"""
+        st = self.st
+        ops.gen_argmax(logits, n_inp, self.gs, self._gen, st.ctl, st.guess, pos, sel, st.am, rows_out)
+
+    def _prefill_pos(self, rows: List[int]) -> torch.Tensor:
+        return torch.tensor(rows, dtype=torch.int32, device=self.e.device)         # a prefill feeds token i at position i
 
     # ---- steady step as ONE hipGraph ------------------------------------------------------------------
     # Fixed shapes: a graph is captured per candidate-count bucket gcap; a step with g candidates replays the
@@ -223,17 +290,22 @@ class LookaheadDecoder:
              ptr(st.ids), ptr(st.pos), None, 0, 1)
         # greedy steps take the row argmax inside the lm_head GEMM (argmax_out: the logits are never materialised); the sampling verify
         # needs the rows themselves
+        # (generation controls: the lm_head materialises the logits, the processed argmax reads them once)
         logits = e.forward(st.ids, st.pos, mask, self._graph_sel[gcap], 1 + W + cand_rows, dyn_P=st.ctl, n_splits=self._graph_splits[gcap],
                            ntk_pad=(st.ctl[CTL_G:CTL_G + 1], gcap, gs),      # (dynamic-NTK RoPE only: the padded candidate slots are not sequence length)
-                           argmax_out=None if forward_only else st.am)
+                           argmax_out=None if (forward_only or self.controls is not None) else st.am)
         if forward_only:
+            if self.controls is not None:
+                rows_out = torch.empty(1 + cand_rows, e.V, dtype=torch.float32, device=e.device)
+                self._gen_rows(logits, W, st.pos, self._graph_sel[gcap], rows_out)
+                return rows_out
             ops.argmax_rows(logits, out=st.am)
             return logits.float()                                   # logits.float(), modeling_llama.py:1544
+        if self.controls is not None:
+            self._gen_rows(logits, W, st.pos, self._graph_sel[gcap])
         # LADE_POLL (default on): the post-step stores the sealed record straight into the pinned host buffer and the host polls for it;
         # otherwise a copy node carries it and the host synchronises the stream
-        call("lade_greedy_post_step", ptr(st.ctl), ptr(st.window), st.wcap, ptr(st.pool_tok), ptr(st.pool_cnt), st.V, W, N, G,
-             ptr(st.am), W, ptr(st.guess), T, cand_rows, 2, int(self.pool_from_prompt), ptr(st.tail), self.eos, None, None, ptr(st.record),
-             ptr(st.record_host) if self.poll else None)
+        self._post_step(st.am, W, T, cand_rows, 2, record_host=st.record_host if self.poll else None)
         ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
         if not self.poll:
             st.record_host.copy_(st.record, non_blocking=True)
@@ -243,6 +315,8 @@ class LookaheadDecoder:
         W, N, gs = self.W, self.N, self.gs
         self._graphs, self._graph_sel, self._graph_splits, self._graph_T, self._graph_logits = {}, {}, {}, {}, {}
         state = (st.ctl, st.window, st.pool_cnt, st.pool_tok, st.guess, st.tail) + (() if e.ntk_state is None else (e.ntk_state,))
+        if self.controls is not None:
+            state += (self._gen,)           # the warm-up's post-step adds its tokens to the seen set
         saved = [t.clone() for t in state]
         for gcap in self._buckets():
             cand_rows = gcap * gs
@@ -272,12 +346,13 @@ class LookaheadDecoder:
         torch.cuda.synchronize()
         st.record_host.zero_()              # the warm-up passes left records of the step number the first replay will produce: never mistake one for it
         self._graph = "forward" if forward_only else "step"
-        self._graph_eos = self.eos
+        self._graph_eos = (self.eos_set, self.controls is not None)        # the control VALUES live in device memory: no re-capture
+        self._graph_ctl = self.controls is not None          # what the body launches (and, sampling, which rows it returns) depends on it
         self._graph_gen = e.generation
 
     def _step_graph(self) -> dict:
         e, st = self.e, self.st
-        if self._graph != "step" or self._graph_eos != self.eos or self._graph_gen != e.generation:
+        if self._graph != "step" or self._graph_eos != (self.eos_set, self.controls is not None) or self._graph_gen != e.generation:
             self._capture_graphs()
         gcap = self._bucket_for(self.g)
         T = self._graph_T[gcap]
@@ -329,9 +404,13 @@ class LookaheadDecoder:
             ids_h = prompt + self.window0
             n_inp, cand_rows = len(self.window0), 0
             # rows whose logits are read: the last prompt token and the window (:1578-1606)
-            logits, done = e.prefill(ids_h, [len(prompt) - 1] + list(range(len(prompt), len(ids_h))))
+            prows = [len(prompt) - 1] + list(range(len(prompt), len(ids_h)))
+            logits, done = e.prefill(ids_h, prows)
             T, P_before = len(ids_h) - done, done
             n_input = len(prompt) - done                             # out row = last prompt token of the last chunk
+            if self.controls is not None:
+                self._gen_rows(logits, n_inp, self._prefill_pos(prows), None)
+                logits = None
         else:
             phase = 2 if fill_level >= N - 2 else 1
             n_input = 1
@@ -345,11 +424,13 @@ class LookaheadDecoder:
             # rows whose logits are needed: out row, last level's rows, candidate rows (:1578-1606)
             rows = [n_input - 1] + list(range(T - cand_rows - n_inp, T - cand_rows)) + list(range(T - cand_rows, T))
             n_sel = self._set_sel(rows)
-            logits = e.forward(st.ids, st.pos, mask, st.sel, n_sel, argmax_out=st.am)
+            logits = e.forward(st.ids, st.pos, mask, st.sel, n_sel, argmax_out=None if self.controls is not None else st.am)
+            if self.controls is not None:
+                self._gen_rows(logits, n_inp, st.pos, st.sel)
+                logits = None
         if logits is not None:                       # the prefill step returns its logits, a decode step has taken the argmax already
             ops.argmax_rows(logits, out=st.am)
-        call("lade_greedy_post_step", ptr(st.ctl), ptr(st.window), st.wcap, ptr(st.pool_tok), ptr(st.pool_cnt), st.V, W, N, G,
-             ptr(st.am), n_inp, ptr(st.guess), T, cand_rows, phase, int(self.pool_from_prompt), ptr(st.tail), self.eos, None, None, ptr(st.record), None)
+        self._post_step(st.am, n_inp, T, cand_rows, phase)
         ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
         rec = st.read_record()
         self._step_no = rec[7]
@@ -365,19 +446,27 @@ class LookaheadDecoder:
 
     @torch.no_grad()
     @_on_device
-    def greedy(self, prompt: Sequence[int], max_length: int, eos_token_id: Optional[int] = None,
-               rng: Optional[random.Random] = None, keep_trace: bool = False, on_step=None) -> GenOut:
+    def greedy(self, prompt: Sequence[int], max_length: int, eos_token_id=None,
+               rng: Optional[random.Random] = None, keep_trace: bool = False, on_step=None, controls: Optional[GenControls] = None) -> GenOut:
         """`jacobi_greedy_search_multilevel` (lade/decoding.py:697-1259), single GPU or lookahead parallel.
         on_step(accepted_tokens): called after every step with the tokens it accepted (chat printing / HF streamers,
         lade/decoding.py:1179-1200)."""
         if self.lp is not None and (self.lp.R > 1 or self.lp.force):
+            # the lookahead-parallel verify and EOS scan (lade_lp_reduce_apply) know neither the controls nor an EOS set
+            if controls is not None and controls.active:
+                raise cabi.LadeHipError("lookahead parallelism (DIST_WORKERS > 1 / FORCE_LP) does not implement repetition_penalty / "
+                                        "min_length / min_new_tokens: run on one GPU without FORCE_LP")
+            eos = eos_set(eos_token_id)
+            if len(eos) > 1:
+                raise cabi.LadeHipError(f"lookahead parallelism (DIST_WORKERS > 1 / FORCE_LP) stops on one EOS id only, got {list(eos)}: "
+                                        "run on one GPU without FORCE_LP")
             from .parallel import greedy_lp
-            out = greedy_lp(self, prompt, max_length, eos_token_id, rng, keep_trace, on_step=on_step)
+            out = greedy_lp(self, prompt, max_length, eos[0] if eos else None, rng, keep_trace, on_step=on_step)
             # the reference logs on rank 0 only (`if DEBUG and LOCAL_RANK == 0`, lade/decoding.py:1231-1235)
             if CONFIG_MAP.get("DEBUG", 0) and self.lp.rank == 0:
                 CONFIG_MAP.setdefault("log", []).append([out.generated, out.steps, round(out.generated / max(out.steps, 1), 2)])
             return out
-        self.start(prompt, eos_token_id, rng)
+        self.start(prompt, eos_token_id, rng, controls)
         trace: List[dict] = []
         while True:
             info = self.step()
@@ -426,12 +515,12 @@ class LookaheadDecoder:
 
     @torch.no_grad()
     @_on_device
-    def sample_start(self, prompt: Sequence[int], warp=None, eos_token_id: Optional[int] = None, rng: Optional[random.Random] = None,
-                     torch_gen: Optional[torch.Generator] = None) -> None:
+    def sample_start(self, prompt: Sequence[int], warp=None, eos_token_id=None, rng: Optional[random.Random] = None,
+                     torch_gen: Optional[torch.Generator] = None, controls: Optional[GenControls] = None) -> None:
         """Begins a sampling run (`sample` = sample_start + sample_step until done; bench.py drives single steps)."""
         e, W = self.e, self.W
         rng = rng if rng is not None else random
-        self.start(prompt, eos_token_id, rng)
+        self.start(prompt, eos_token_id, rng, controls)
         if torch_gen is not None and torch_gen.device.type == "cuda" and not getattr(self, "_draw_warm", False):
             # the draw's torch kernels (exponential, divide, argmax, and the strike-and-renormalise ops of a rejected draft) load their code
             # objects on first use: 10-26 ms in the middle of the first step that rejects a draft.  One dry run on a throw-away generator -
@@ -447,9 +536,9 @@ class LookaheadDecoder:
 
     @torch.no_grad()
     @_on_device
-    def sample(self, prompt: Sequence[int], max_length: int, warp=None, eos_token_id: Optional[int] = None,
+    def sample(self, prompt: Sequence[int], max_length: int, warp=None, eos_token_id=None,
                rng: Optional[random.Random] = None, torch_gen: Optional[torch.Generator] = None, keep_trace: bool = False,
-               on_step=None) -> GenOut:
+               on_step=None, controls: Optional[GenControls] = None) -> GenOut:
         """`jacobi_sample_multilevel` (lade/decoding.py:137-692), single GPU (the reference has no LP here).
 
         The model step, input assembly, pool and window stay on the GPU, and so do the probabilities: `lade_softmax_gather`
@@ -458,7 +547,7 @@ class LookaheadDecoder:
         one `torch.multinomial` for the token that ends the step (:484-540), and the `filter_window` draws (:578-580).
         `warp`: a sampling.Warper (temperature / top-k / top-p; temperature alone is applied inside the kernels) or any callable
         mapping fp32 logits rows [r, V] to warped logits (the HF warpers the reference admits, :375-377)."""
-        self.sample_start(prompt, warp, eos_token_id, rng, torch_gen)
+        self.sample_start(prompt, warp, eos_token_id, rng, torch_gen, controls)
         trace: List[dict] = []
         while True:
             info = self.sample_step(keep_trace)
@@ -491,13 +580,20 @@ class LookaheadDecoder:
             phase = 0
             ids_h = prompt_l + self.window0
             n_inp, cand_rows = len(self.window0), 0
-            logits, done = e.prefill(ids_h, [len(prompt_l) - 1] + list(range(len(prompt_l), len(ids_h))))
-            logits = logits.float()
-            ops.argmax_rows(logits, out=st.am)
+            prows = [len(prompt_l) - 1] + list(range(len(prompt_l), len(ids_h)))
+            logits, done = e.prefill(ids_h, prows)
+            if self.controls is not None:
+                rows_out = torch.empty(1, e.V, dtype=torch.float32, device=e.device)
+                self._gen_rows(logits, n_inp, self._prefill_pos(prows), None, rows_out)
+                logits = rows_out
+            else:
+                logits = logits.float()
+                ops.argmax_rows(logits, out=st.am)
             T, P_before = len(ids_h) - done, done
         elif self.use_graph and fill_level >= N - 2:
             # steady step: input assembly + model step + argmax replayed as one hipGraph (candidate rows padded to the bucket)
-            if self._graph != "forward" or self._graph_gen != e.generation:
+            # controls on: the body returns the processed out / candidate rows (no window rows); off: logits.float() of every row
+            if self._graph != "forward" or self._graph_ctl != (self.controls is not None) or self._graph_gen != e.generation:
                 self._capture_graphs(forward_only=True)
             phase, n_inp = 2, W
             gcap = self._bucket_for(g)
@@ -518,8 +614,15 @@ class LookaheadDecoder:
                  ptr(st.guess), g if phase == 2 else 0, gs, cand_rows, ptr(st.ids), ptr(st.pos), None, 0, 1)
             n_inp = ls[-1]
             n_sel = self._set_sel([0] + list(range(T - cand_rows - n_inp, T - cand_rows)) + list(range(T - cand_rows, T)))
-            logits = e.forward(st.ids, st.pos, mask, st.sel, n_sel).float()    # logits.float(), modeling_llama.py:1544
-            ops.argmax_rows(logits, out=st.am)                                    # window levels are filled by argmax (:459, :545)
+            if self.controls is not None:
+                rows_out = torch.empty(1 + cand_rows, e.V, dtype=torch.float32, device=e.device)
+                self._gen_rows(e.forward(st.ids, st.pos, mask, st.sel, n_sel), n_inp, st.pos, st.sel, rows_out)
+                logits = rows_out
+            else:
+                logits = e.forward(st.ids, st.pos, mask, st.sel, n_sel).float()    # logits.float(), modeling_llama.py:1544
+                ops.argmax_rows(logits, out=st.am)                                    # window levels are filled by argmax (:459, :545)
+        # generation controls: `logits` holds the processed fp32 out row and candidate rows only (lade_gen_rows), no window rows between
+        n_skip = 0 if self.controls is not None else n_inp
         step_inputs = {}
         if keep_trace and phase != 0:                            # what the step fed and judged (tests re-derive the probabilities)
             step_inputs = dict(ids=st.ids[:T].tolist(), pos=st.pos[:T].tolist(), level_sizes=list(self._level_sizes(fill_level)),
@@ -528,13 +631,13 @@ class LookaheadDecoder:
         verify = phase == 2 and g > 0
         rows = 1 + g * gs if verify else 1
         if fused_T is not None:                              # temperature only: the kernels scale the logits themselves
-            src, skip, temp = logits, n_inp, fused_T
+            src, skip, temp = logits, n_skip, fused_T
         else:
             # top-k / top-p: one device launch over the out row and the candidate rows (lade_warp_rows); HF warper objects and
             # vocabularies beyond that kernel: torch ops on the device
-            src = warp.warp_rows(logits, rows, n_inp) if hasattr(warp, "warp_rows") else None
+            src = warp.warp_rows(logits, rows, n_skip) if hasattr(warp, "warp_rows") else None
             if src is None:
-                picked = logits[0:1] if not verify else torch.cat([logits[0:1], logits[1 + n_inp:1 + n_inp + g * gs]])
+                picked = logits[0:1] if not verify else torch.cat([logits[0:1], logits[1 + n_skip:1 + n_skip + g * gs]])
                 src = warp(picked)
             skip, temp = 0, 1.0
         max_hit_idx = 0
@@ -557,10 +660,10 @@ class LookaheadDecoder:
         if drawn_on_device is not None:
             hits[-1] = 0
         level_override = None
-        if phase == 2 and self.eos >= 0:                                      # filter_window on the new level (:578-580)
+        if phase == 2 and self.eos_set:                                       # filter_window on the new level (:578-580), any EOS id
             buf["am_host"].copy_(st.am[1:1 + W], non_blocking=True)
             torch.cuda.current_stream().synchronize()
-            repl = [rng.choice(all_old_tokens) if tok == self.eos else -1 for tok in buf["am_host"].tolist()]
+            repl = [rng.choice(all_old_tokens) if tok in self.eos_set else -1 for tok in buf["am_host"].tolist()]
             if any(x >= 0 for x in repl):
                 override.copy_(torch.tensor(repl, dtype=torch.int32))
                 level_override = override
@@ -570,9 +673,7 @@ class LookaheadDecoder:
         forced.copy_(buf["forced_host"], non_blocking=True)
         if drawn_on_device is not None:
             forced[2 + max_hit:3 + max_hit].copy_(drawn_on_device)          # the drawn token never left the device
-        call("lade_greedy_post_step", ptr(st.ctl), ptr(st.window), st.wcap, ptr(st.pool_tok), ptr(st.pool_cnt), st.V, W, N, G,
-             ptr(st.am), n_inp, ptr(st.guess), T, cand_rows, phase, int(self.pool_from_prompt), ptr(st.tail), self.eos,
-             ptr(forced), ptr(level_override), ptr(st.record), None)
+        self._post_step(st.am, n_inp, T, cand_rows, phase, forced=forced, level_override=level_override)
         ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
         rec = st.read_record()
         self._step_no = rec[7]

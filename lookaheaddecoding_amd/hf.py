@@ -21,7 +21,7 @@ from typing import Optional
 import torch
 
 from . import cabi
-from .decoding import CONFIG_MAP, FUNC_MAP, LookaheadDecoder
+from .decoding import CONFIG_MAP, FUNC_MAP, GenControls, LookaheadDecoder, eos_set
 from .engine import StepEngine
 
 _ENGINE_ATTR = "_lade_engine"
@@ -248,18 +248,46 @@ def jforward_multilevel(self, input_ids=None, past_tokens=None, guess_tokens=Non
 
 
 def _criteria_limits(stopping_criteria, generation_config=None):
+    """(max_length, EOS ids) of HF's stopping criteria: the smallest max_length and the whole id set of the first EOS criterion"""
     max_length, eos = None, None
     for c in (stopping_criteria or []):
         if hasattr(c, "max_length") and c.max_length is not None:
             max_length = int(c.max_length) if max_length is None else min(max_length, int(c.max_length))
         if hasattr(c, "eos_token_id") and eos is None:
-            e = c.eos_token_id
-            e = e.tolist() if hasattr(e, "tolist") else e
-            eos = e[0] if isinstance(e, (list, tuple)) else e
+            eos = eos_set(c.eos_token_id) or None
     return max_length, eos
 
 
-def _run(self, input_ids, do_sample, warp, stopping_criteria, eos_token_id, generation_config, streamer, chat):
+def controls_from_processors(processors):
+    """Splits HF's logits-processor list into what the device step applies and the rest: (GenControls or None, remaining).
+    Taken: RepetitionPenaltyLogitsProcessor (without prompt_ignore_length), MinLengthLogitsProcessor, MinNewTokensLengthLogitsProcessor.
+    Everything else stays in `remaining` (the temperature / top-k / top-p warpers of a sampling call, or a processor the callers refuse
+    as before).  HF applies processors before warpers; a taken processor placed after a warper is refused (AssertionError), since the
+    device step applies the controls to the raw logits."""
+    from transformers.generation import logits_process as lp
+    warper_kinds = (lp.TemperatureLogitsWarper, lp.TopKLogitsWarper, lp.TopPLogitsWarper)
+    penalty, min_len, mask_eos, rest = 1.0, 0, None, []
+    for p in (processors or []):
+        kind = type(p)
+        taken = ((kind is lp.RepetitionPenaltyLogitsProcessor and not getattr(p, "prompt_ignore_length", None) and penalty == 1.0)
+                 or (kind in (lp.MinLengthLogitsProcessor, lp.MinNewTokensLengthLogitsProcessor)
+                     and (mask_eos is None or eos_set(p.eos_token_id) == mask_eos)))
+        if not taken:
+            rest.append(p)
+            continue
+        assert not any(type(q) in warper_kinds for q in rest), \
+            f"{kind.__name__} after a logits warper: lookahead applies repetition_penalty / min length before the warpers (HF's order)"
+        if kind is lp.RepetitionPenaltyLogitsProcessor:
+            penalty = float(p.penalty)
+        else:
+            mask_eos = eos_set(p.eos_token_id)
+            need = p.min_length if kind is lp.MinLengthLogitsProcessor else p.prompt_length_to_skip + p.min_new_tokens
+            min_len = max(min_len, int(need))
+    ctl = GenControls(penalty, min_len, mask_eos)
+    return (ctl if ctl.active else None), rest
+
+
+def _run(self, input_ids, do_sample, warp, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls=None):
     W = CONFIG_MAP.get("WINDOW_SIZE", 60)            # reference defaults when config_lade was never called
     G = CONFIG_MAP.get("GUESS_SET_SIZE", 60)         # (lade/decoding.py:854-857)
     N = CONFIG_MAP.get("LEVEL", 8)
@@ -267,8 +295,7 @@ def _run(self, input_ids, do_sample, warp, stopping_criteria, eos_token_id, gene
     assert input_ids.size(0) == 1, " single batch only "      # modeling_llama.py:1448
     R = CONFIG_MAP.get("DIST_WORKERS", 1)
     max_length, eos_c = _criteria_limits(stopping_criteria, generation_config)
-    if isinstance(eos_token_id, (list, tuple)):
-        eos_token_id = eos_token_id[0] if eos_token_id else None
+    eos_token_id = eos_set(eos_token_id) or None           # every EOS id counts (Llama-3.x-Instruct ships three)
     if eos_token_id is None:
         eos_token_id = eos_c
     if max_length is None:
@@ -312,9 +339,9 @@ def _run(self, input_ids, do_sample, warp, stopping_criteria, eos_token_id, gene
 
     cb = on_step if (streamer is not None or tok is not None) else None
     if do_sample:
-        out = dec.sample(prompt, max_length, warp=warp, eos_token_id=eos_token_id, rng=random, on_step=cb)
+        out = dec.sample(prompt, max_length, warp=warp, eos_token_id=eos_token_id, rng=random, on_step=cb, controls=controls)
     else:
-        out = dec.greedy(prompt, max_length, eos_token_id=eos_token_id, rng=random, on_step=cb)
+        out = dec.greedy(prompt, max_length, eos_token_id=eos_token_id, rng=random, on_step=cb, controls=controls)
     if CONFIG_MAP.get("DEBUG", 0) and rank0:
         print("\n==========================ACCELERATION===SUMMARY======================================")
         print("Generated tokens: ", out.generated, "Total steps: ", out.steps, " Compression ratio: ", round(out.generated / max(out.steps, 1), 2))
@@ -331,11 +358,12 @@ def jacobi_greedy_search_multilevel(self, input_ids, logits_processor=None, stop
                                     generation_config=None, **model_kwargs):
     """Same call contract as lade/decoding.py:697-715 (extras `chat`, `stop_token`); returns LongTensor [1, len]."""
     assert not return_dict_in_generate, "return_dict_in_generate is not supported (lade/decoding.py:967)"
+    controls, logits_processor = controls_from_processors(logits_processor)       # repetition penalty / min length run on the device
     assert logits_processor is None or len(logits_processor) == 0, "logits processors are not supported in greedy lookahead (:968)"
     if max_length is not None:
         from transformers.generation.stopping_criteria import MaxLengthCriteria, StoppingCriteriaList
         stopping_criteria = StoppingCriteriaList(list(stopping_criteria or []) + [MaxLengthCriteria(max_length)])
-    return _run(self, input_ids, False, None, stopping_criteria, eos_token_id, generation_config, streamer, chat)
+    return _run(self, input_ids, False, None, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls)
 
 
 def _canonical_warper(warpers, T_cls, K_cls, P_cls):
@@ -362,9 +390,12 @@ def _canonical_warper(warpers, T_cls, K_cls, P_cls):
 def jacobi_sample_multilevel(self, input_ids, logits_processor=None, stopping_criteria=None, logits_warper=None, max_length=None,
                              pad_token_id=None, eos_token_id=None, output_attentions=None, output_hidden_states=None, output_scores=None,
                              return_dict_in_generate=None, synced_gpus=False, streamer=None, chat=False, generation_config=None,
-                             **model_kwargs):
-    """Same call contract as lade/decoding.py:137-154.  Warpers are restricted like the reference (:375-377)."""
+                             controls=None, **model_kwargs):
+    """Same call contract as lade/decoding.py:137-154.  Warpers are restricted like the reference (:375-377); repetition penalty and
+    min length among the logits processors run on the device (`controls`: already split off by _sample_proxy)."""
     assert not return_dict_in_generate
+    if controls is None:
+        controls, _ = controls_from_processors(logits_processor)
     from transformers.generation.logits_process import TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper
     warpers = list(logits_warper or [])
     for wp in warpers:
@@ -382,7 +413,7 @@ def jacobi_sample_multilevel(self, input_ids, logits_processor=None, stopping_cr
                 scores = wp(input_ids, scores)
             return scores
 
-    return _run(self, input_ids, True, warp, stopping_criteria, eos_token_id, generation_config, streamer, chat)
+    return _run(self, input_ids, True, warp, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls)
 
 
 def greedy_search_proxy(self, *args, **kwargs):
@@ -414,10 +445,10 @@ def _sample_proxy(self, input_ids, logits_processor=None, stopping_criteria=None
     assert not generation_config.return_dict_in_generate, "return_dict_in_generate is not supported"
     if generation_config.do_sample:
         from transformers.generation.logits_process import TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper
-        warpers = [p for p in (logits_processor or [])]
+        controls, warpers = controls_from_processors(logits_processor)      # processors first, then the warpers (HF's order)
         for wp in warpers:
             assert type(wp) in (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper), f"please set top_k=0.0 and top_p=1.0 {wp}"
         return jacobi_sample_multilevel(self, input_ids, stopping_criteria=stopping_criteria, logits_warper=warpers, streamer=streamer,
-                                        chat=chat, generation_config=generation_config)
+                                        chat=chat, generation_config=generation_config, controls=controls)
     return jacobi_greedy_search_multilevel(self, input_ids, logits_processor=logits_processor, stopping_criteria=stopping_criteria,
                                            streamer=streamer, chat=chat, generation_config=generation_config)

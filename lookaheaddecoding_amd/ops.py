@@ -482,3 +482,35 @@ def rope_kv_append_parts_ex(part: torch.Tensor, n_parts: int, q_out: torch.Tenso
     """rope_kv_append_parts with the qkv epilogue: the bias joins the fp32 sum of the partials before its one rounding"""
     call("lade_rope_kv_append_parts_ex", ptr(part), n_parts, T * (H + 2 * Hkv) * d, ptr(q_out), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache),
          ptr(vt_cache), T, P, ptr(dyn_P), H, Hkv, d, k_cache.shape[1], cos.shape[0], dtype_code(q_out), None if epi is None else C.byref(epi))
+
+
+# ---- generation controls (repetition penalty, min length; include/lade_hip.h "generation controls") -------------------------------
+def host_ids(ids) -> "C.Array":
+    """a host int32 array for the entry points that copy a short id list into their launch (EOS sets)"""
+    import ctypes as C
+    return (C.c_int32 * max(len(ids), 1))(*[int(t) for t in ids])
+
+
+def gen_ctl_init(gen: torch.Tensor, V: int, penalty: float, min_len: int, eos_ids, prompt: torch.Tensor) -> None:
+    """penalty / min_len / the min-length EOS ids into the control block, seen set = the prompt tokens (device int32)"""
+    assert gen.dtype == torch.int32 and gen.numel() >= cabi.gen_words(V) and prompt.dtype == torch.int32
+    call("lade_gen_ctl_init", ptr(gen), V, float(penalty), int(min_len), host_ids(eos_ids), len(eos_ids), ptr(prompt), prompt.numel())
+
+
+def gen_ctl_update(gen: torch.Tensor, ctl: torch.Tensor) -> None:
+    call("lade_gen_ctl_update", ptr(gen), ptr(ctl))
+
+
+def gen_argmax(logits: torch.Tensor, n_inp: int, gs: int, gen: torch.Tensor, ctl: torch.Tensor, guess: torch.Tensor, pos: torch.Tensor,
+               sel: Optional[torch.Tensor], am: torch.Tensor, rows_out: Optional[torch.Tensor] = None) -> None:
+    """Processed row argmax of a step's logits [out | n_inp window | candidates] (lade_gen_argmax); with rows_out [1 + cand_rows, V]
+    fp32 also the processed out / candidate rows (lade_gen_rows)."""
+    _dev(logits, "logits")
+    assert logits.dim() == 2 and logits.stride(1) == 1 and am.dtype == torch.int32 and am.numel() >= logits.shape[0]
+    rows, V = logits.shape
+    args = (ptr(logits), logits.stride(0), rows, V, dtype_code(logits), n_inp, gs, ptr(gen), ptr(ctl), ptr(guess), ptr(pos), ptr(sel), ptr(am))
+    if rows_out is None:
+        call("lade_gen_argmax", *args)
+    else:
+        assert rows_out.dtype == torch.float32 and rows_out.is_contiguous() and rows_out.numel() >= (rows - n_inp) * V
+        call("lade_gen_rows", *args, ptr(rows_out))
