@@ -14,7 +14,7 @@ import random
 import sys
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -68,6 +68,86 @@ class GenOut:
     steps: int
     generated: int
     trace: List[dict] = field(default_factory=list)
+
+
+# ---- the shape of one decode step: plain host arithmetic, shared by the single-GPU decoder and lookahead parallelism -------------
+def level_sizes(W: int, N: int, fill_level: int) -> List[int]:
+    """Lengths of window levels 0..fill_level before the step with that fill level
+    (init W+N-3 at lade/decoding.py:902; each fill step trims one: :1040, :1050-1051)."""
+    if fill_level == 0:
+        return [W + N - 3]
+    if fill_level >= N - 2:
+        return [W - 1] + [W] * (N - 2)
+    return [W + N - 3 - fill_level] + [W + N - 2 - fill_level] * fill_level
+
+
+class StepShape(NamedTuple):
+    """What one step feeds: n_input re-fed tokens | the window levels | cand_rows candidate tokens.  phase: 0 prefill, 1 fill, 2 steady.
+    (A tuple: the lookahead-parallel loop builds one per step between a synchronise and the next launch.)"""
+    phase: int
+    n_input: int
+    level_sizes: tuple
+    cand_rows: int
+
+    @property
+    def T(self) -> int:
+        return self.n_input + sum(self.level_sizes) + self.cand_rows
+
+    @property
+    def n_inp(self) -> int:
+        return self.level_sizes[-1]
+
+    def rows(self) -> List[int]:
+        """rows whose logits are needed: out row, last level's rows, candidate rows (:1578-1606)"""
+        T = self.T
+        return [self.n_input - 1] + list(range(T - self.cand_rows - self.n_inp, T))
+
+
+def step_shape(W: int, N: int, step: int, g: int, n_input: int = 1) -> StepShape:
+    """Shape of step number `step` of a run (0 = prefill, n_input = prompt length; then one fill step per level until fill level
+    N-2, steady from there on) that carries g candidates of N-1 tokens - only a steady step verifies candidates."""
+    fill_level = min(step, N - 2)
+    phase = 0 if step == 0 else (2 if fill_level >= N - 2 else 1)
+    return StepShape(phase, n_input, tuple(level_sizes(W, N, fill_level)), g * (N - 1) if phase == 2 else 0)
+
+
+def capture_step_graph(body, state: Sequence[torch.Tensor], **graph_kw):
+    """`body` as a hipGraph: one warm-up run on a side stream (library handles, allocator, autotune), then the integer `state` it
+    advanced is restored - also when the warm-up failed -, then the capture.  The K/V rows the warm-up wrote lie at >= P and are
+    rewritten by the real step before being read.  Returns (graph, what body returned under capture)."""
+    saved = [t.clone() for t in state]
+    try:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            body()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+    finally:
+        for t, sv in zip(state, saved):
+            t.copy_(sv)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, **graph_kw):
+        out = body()
+    return g, out
+
+
+def generate_loop(run, step, max_length: int, keep_trace: bool, on_step, log: bool) -> GenOut:
+    """step() until EOS or max_length (stopping criteria, lade/decoding.py:1204-1219) on a started `run` (tokens / prompt / steps /
+    finished_by_eos: a LookaheadDecoder or a parallel.LPRunner).  on_step gets each step's accepted tokens, trimmed to max_length."""
+    trace: List[dict] = []
+    while True:
+        info = step()
+        if keep_trace:
+            trace.append(info)
+        if on_step is not None:
+            on_step(info["accepted"][:max(0, max_length - (len(run.tokens) - len(info["accepted"])))])
+        if run.finished_by_eos or len(run.tokens) >= max_length:
+            break
+    generated = min(len(run.tokens), max_length) - len(run.prompt)
+    if log and CONFIG_MAP.get("DEBUG", 0):
+        CONFIG_MAP.setdefault("log", []).append([generated, run.steps, round(generated / max(run.steps, 1), 2)])
+    return GenOut(tokens=run.tokens[:max_length], steps=run.steps, generated=generated, trace=trace)
 
 
 class LadeState:
@@ -127,7 +207,7 @@ class LadeState:
         The spin is bounded by WALL-CLOCK time (LADE_POLL_TIMEOUT_MS, default 250 ms - far beyond any step) and yields the GIL every 256
         reads, so that a streamer thread or lookahead-parallel rank threads of this process are not starved while this one waits.  None
         when the record does not arrive in time - e.g. pinned memory the device's stores do not reach coherently (HIP_HOST_COHERENT=0);
-        the caller then synchronises the stream, reads the record the slow way and STOPS polling for good (LookaheadDecoder._step_graph)."""
+        the caller then synchronises the stream, reads the record the slow way and STOPS polling for good (LookaheadDecoder._polled_record)."""
         buf = self.record_host_np
         deadline = time.monotonic() + (self.POLL_TIMEOUT_S if timeout_s is None else timeout_s)
         while True:
@@ -150,7 +230,6 @@ class LookaheadDecoder:
     def __init__(self, engine: StepEngine, W: int, N: int, G: int, pool_from_prompt: bool = False, lp=None, use_graph: bool = False):
         self.e = engine
         self.use_graph = bool(use_graph)
-        self._graph = None
         # GUESS_SET_SIZE <= 0 (-1 = "unlimited" in the reference's README): both reference loops gate the verification
         # branch on `GUESS_SET_SIZE > 0` (lade/decoding.py:402, :948), so the pool is filled but never read and every
         # step accepts exactly one token.  Reproduced as G = 0: no pool, no candidates.
@@ -164,6 +243,20 @@ class LookaheadDecoder:
         self.st = LadeState(engine.V, W, N, G, engine.device, engine.max_T)
         if self.max_step_tokens() > engine.max_T:
             raise cabi.LadeHipError(f"W={W} N={N} G={G} needs {self.max_step_tokens()} tokens per step > engine.max_T={engine.max_T}")
+        # host state of the current run (start / sample_start)
+        self.prompt, self.window0, self.tokens = [], [], []
+        self.eos_set, self.eos, self.controls = (), -1, None
+        self.steps, self.P, self.g, self.fill_level = 0, 0, 0, 0
+        self.finished_by_eos = False
+        self._s = None                    # the sampling run's warper, RNGs and forced-hits buffers (sample_start)
+        # allocated on first use: a decoder that never gets controls / never samples holds neither
+        self._gen = None                  # generation-control block (start)
+        self._smp = None                  # pinned and device sampling buffers (_sampling_buffers)
+        self._draw_warm = False           # the device draw's torch kernels have run once (sample_start)
+        self._sel_cache = {}              # device copies of the eager steps' logits-row selections (_set_sel)
+        # captured steady steps, per candidate bucket (_capture_graphs); _graph_key: what they were captured for (_graph_key_for)
+        self._graphs, self._graph_sel, self._graph_splits, self._graph_T, self._graph_logits = {}, {}, {}, {}, {}
+        self._graph_key = None
         # every kernel decision the steady steps of this configuration need (GEMM shapes, the in-step pass, the attention launch
         # parameters) is taken NOW, not inside the first live step of each row class (a multi-second stall for that request)
         if lp is None and os.environ.get("LADE_PREPARE", "1") != "0":
@@ -173,21 +266,11 @@ class LookaheadDecoder:
         return self.gs + (self.N - 1) * self.W + self.G * self.gs
 
     # ---- helpers --------------------------------------------------------------------------------
-    def _level_sizes(self, fill_level: int) -> List[int]:
-        """Lengths of window levels 0..fill_level before the step with that fill level
-        (init W+N-3 at lade/decoding.py:902; each fill step trims one: :1040, :1050-1051)."""
-        W, N = self.W, self.N
-        if fill_level == 0:
-            return [W + N - 3]
-        if fill_level >= N - 2:
-            return [W - 1] + [W] * (N - 2)
-        return [W + N - 3 - fill_level] + [W + N - 2 - fill_level] * fill_level
-
     def _set_sel(self, rows: List[int]) -> int:
         """Device copy of the logits-row selection.  The selections of a run are a handful of shapes (one per phase / candidate
         count), so each is uploaded once and kept: a steady eager step issues no host-to-device copy for it."""
         key = (rows[0], rows[1] if len(rows) > 1 else -1, len(rows), rows[-1])
-        cache = self.__dict__.setdefault("_sel_cache", {})
+        cache = self._sel_cache
         t = cache.get(key)
         if t is None:
             if len(cache) > 256:
@@ -218,7 +301,7 @@ class LookaheadDecoder:
         self.eos = self.eos_set[0] if self.eos_set else -1
         self.controls = controls if controls is not None and controls.active else None
         if self.controls is not None:
-            if getattr(self, "_gen", None) is None:
+            if self._gen is None:
                 self._gen = torch.zeros(cabi.gen_words(st.V), dtype=torch.int32, device=e.device)
             c = self.controls
             mask_eos = self.eos_set if c.min_len_eos is None else eos_set(c.min_len_eos)
@@ -243,13 +326,55 @@ class LookaheadDecoder:
         if self.controls is not None:
             ops.gen_ctl_update(self._gen, st.ctl)
 
-    def _gen_rows(self, logits: torch.Tensor, n_inp: int, pos: torch.Tensor, sel: Optional[torch.Tensor], rows_out=None) -> None:
-        """processed argmax of a step's rows into st.am (and the processed fp32 out / candidate rows into rows_out)"""
+    def _logits_to_am(self, logits: Optional[torch.Tensor], shape: StepShape, pos: torch.Tensor, sel: Optional[torch.Tensor], want_rows: bool,
+                      captured: bool = False) -> Optional[torch.Tensor]:
+        """The step's argmax ids into st.am.  want_rows (sampling): also returns the fp32 rows the verify reads - logits.float() of every
+        selected row (modeling_llama.py:1544), or under generation controls the PROCESSED out row and candidate rows only (lade_gen_rows:
+        no window rows between).  logits None: the lm_head GEMM has taken the argmax already."""
         st = self.st
-        ops.gen_argmax(logits, n_inp, self.gs, self._gen, st.ctl, st.guess, pos, sel, st.am, rows_out)
+        if self.controls is not None:
+            rows_out = torch.empty(1 + shape.cand_rows, st.V, dtype=torch.float32, device=self.e.device) if want_rows else None
+            ops.gen_argmax(logits, shape.n_inp, self.gs, self._gen, st.ctl, st.guess, pos, sel, st.am, rows_out)
+            return rows_out
+        if logits is None:
+            return None
+        if want_rows and not captured:                    # (the captured forward-only body converts AFTER the argmax: the order of its launches is kept)
+            logits = logits.float()
+        ops.argmax_rows(logits, out=st.am)                # window levels are filled by argmax (:459, :545)
+        return logits.float() if want_rows else None      # (fp32 already: itself)
 
-    def _prefill_pos(self, rows: List[int]) -> torch.Tensor:
-        return torch.tensor(rows, dtype=torch.int32, device=self.e.device)         # a prefill feeds token i at position i
+    def _model_step(self, shape: StepShape, want_rows: bool, P: int, g: int, sel: Optional[torch.Tensor] = None, c0: int = 0, c1: int = -1,
+                    guess: Optional[int] = None, lp=(0, 1), **device_len) -> Optional[torch.Tensor]:
+        """The front end of every decode step after the prefill: input assembly, the model over the step's T tokens, argmax ids into
+        st.am; returns what _logits_to_am returns.  Eager: P and g (candidates among `guess`) are this step's values.  Captured:
+        P = 0, g = -1, the logits rows `sel` of the capture and device_len (dyn_P, n_splits, ntk_pad) - the kernels read cache length
+        and candidate count from the control block.  Lookahead parallelism feeds window columns [c0, c1), its share of the guesses
+        and, captured, lp = (rank, world).
+        Greedy steps take the row argmax inside the lm_head GEMM (argmax_out: the logits are never materialised); the sampling verify
+        needs the rows themselves, and under generation controls the lm_head materialises them and the processed argmax reads them once."""
+        e, st, gs = self.e, self.st, self.gs
+        mask = StepMask.from_levels(shape.n_input, shape.level_sizes, shape.cand_rows, gs, P)
+        call("lade_build_inputs", None, None, shape.n_input, ptr(st.window), st.wcap, ptr(st.ctl), len(shape.level_sizes) - 1, c0, c1,
+             ptr(st.guess) if guess is None else guess, g, gs, shape.cand_rows, ptr(st.ids), ptr(st.pos), None, *lp)
+        if sel is None:                  # eager: shape.rows(), cached on the device per shape - no host-to-device copy in a steady step
+            sel, n_sel = st.sel, self._set_sel(shape.rows())
+        else:
+            n_sel = sel.numel()
+        logits = e.forward(st.ids, st.pos, mask, sel, n_sel, argmax_out=None if (want_rows or self.controls is not None) else st.am, **device_len)
+        return self._logits_to_am(logits, shape, st.pos, sel, want_rows, captured=bool(device_len))
+
+    def _eager_model(self, want_rows: bool):
+        """The prefill, or an eager decode step, up to the argmax ids in st.am: (shape, T, P_before, rows or None)"""
+        e, st = self.e, self.st
+        shape = step_shape(self.W, self.N, self.steps, self.g, len(self.prompt) if self.steps == 0 else 1)
+        if shape.phase == 0:                                         # prefill: prompt + L0, plain causal
+            # rows whose logits are read: the last prompt token and the window (:1578-1606)
+            prows = shape.rows()
+            logits, done = e.prefill(self.prompt + self.window0, prows)
+            pos = torch.tensor(prows, dtype=torch.int32, device=e.device) if self.controls is not None else None      # a prefill feeds token i at position i
+            return shape, shape.T - done, done, self._logits_to_am(logits, shape, pos, None, want_rows)
+        rows = self._model_step(shape, want_rows, self.P, shape.cand_rows // self.gs)
+        return shape, shape.T, self.P, rows
 
     # ---- steady step as ONE hipGraph ------------------------------------------------------------------
     # Fixed shapes: a graph is captured per candidate-count bucket gcap; a step with g candidates replays the
@@ -278,90 +403,66 @@ class LookaheadDecoder:
             raise cabi.LadeHipError(f"KV cache exhausted: P={self.P}, a step with {g} candidates no longer fits S_max={self.e.S_max}")
         return min(fits)
 
-    def _graph_body(self, gcap: int, forward_only: bool = False):
+    def _graph_body(self, shape: StepShape, gcap: int, forward_only: bool):
         """forward_only (sampling): input assembly + model step + argmax; the fp32 logits of the selected rows stay in
         the graph's memory pool for the host-side verify, the post-step is launched afterwards with the forced hits."""
         e, st = self.e, self.st
-        W, N, G, gs = self.W, self.N, self.G, self.gs
-        cand_rows = gcap * gs
-        mask = StepMask.from_levels(1, self._level_sizes(N - 2), cand_rows, gs, 0)
-        T = mask.T
-        call("lade_build_inputs", None, None, 1, ptr(st.window), st.wcap, ptr(st.ctl), N - 2, 0, -1, ptr(st.guess), -1, gs, cand_rows,
-             ptr(st.ids), ptr(st.pos), None, 0, 1)
-        # greedy steps take the row argmax inside the lm_head GEMM (argmax_out: the logits are never materialised); the sampling verify
-        # needs the rows themselves
-        # (generation controls: the lm_head materialises the logits, the processed argmax reads them once)
-        logits = e.forward(st.ids, st.pos, mask, self._graph_sel[gcap], 1 + W + cand_rows, dyn_P=st.ctl, n_splits=self._graph_splits[gcap],
-                           ntk_pad=(st.ctl[CTL_G:CTL_G + 1], gcap, gs),      # (dynamic-NTK RoPE only: the padded candidate slots are not sequence length)
-                           argmax_out=None if (forward_only or self.controls is not None) else st.am)
+        rows = self._model_step(shape, forward_only, 0, -1, self._graph_sel[gcap], dyn_P=st.ctl,
+                                n_splits=self._graph_splits[gcap],
+                                ntk_pad=(st.ctl[CTL_G:CTL_G + 1], gcap, self.gs))      # (dynamic-NTK RoPE only: the padded candidate slots are not sequence length)
         if forward_only:
-            if self.controls is not None:
-                rows_out = torch.empty(1 + cand_rows, e.V, dtype=torch.float32, device=e.device)
-                self._gen_rows(logits, W, st.pos, self._graph_sel[gcap], rows_out)
-                return rows_out
-            ops.argmax_rows(logits, out=st.am)
-            return logits.float()                                   # logits.float(), modeling_llama.py:1544
-        if self.controls is not None:
-            self._gen_rows(logits, W, st.pos, self._graph_sel[gcap])
+            return rows
         # LADE_POLL (default on): the post-step stores the sealed record straight into the pinned host buffer and the host polls for it;
         # otherwise a copy node carries it and the host synchronises the stream
-        self._post_step(st.am, W, T, cand_rows, 2, record_host=st.record_host if self.poll else None)
+        self._post_step(st.am, shape.n_inp, shape.T, shape.cand_rows, 2, record_host=st.record_host if self.poll else None)
         ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
         if not self.poll:
             st.record_host.copy_(st.record, non_blocking=True)
 
+    def _graph_key_for(self, forward_only: bool) -> tuple:
+        """What captured graphs depend on: the kind of body, whether it launches the generation controls (their VALUES live in device
+        memory: no re-capture), the engine's generation, and - only for the body that contains the post-step - the EOS set."""
+        return (forward_only, self.controls is not None, self.e.generation, None if forward_only else self.eos_set)
+
     def _capture_graphs(self, forward_only: bool = False) -> None:
         e, st = self.e, self.st
-        W, N, gs = self.W, self.N, self.gs
         self._graphs, self._graph_sel, self._graph_splits, self._graph_T, self._graph_logits = {}, {}, {}, {}, {}
         state = (st.ctl, st.window, st.pool_cnt, st.pool_tok, st.guess, st.tail) + (() if e.ntk_state is None else (e.ntk_state,))
         if self.controls is not None:
             state += (self._gen,)           # the warm-up's post-step adds its tokens to the seen set
-        saved = [t.clone() for t in state]
         for gcap in self._buckets():
-            cand_rows = gcap * gs
-            T = (N - 1) * W + cand_rows
+            shape = StepShape(2, 1, tuple(level_sizes(self.W, self.N, self.N - 2)), gcap * self.gs)
+            T = shape.T
             if self.P + T > e.S_max:
-                # the warm-up below runs the whole step body at the current cache length: a bucket that no longer fits would
-                # write its K/V rows past the cache.  Such a bucket can never be replayed either (_step_graph checks), skip it.
+                # the warm-up runs the whole step body at the current cache length: a bucket that no longer fits would
+                # write its K/V rows past the cache.  Such a bucket can never be replayed either (_replay checks), skip it.
                 continue
-            rows = [0] + list(range(T - cand_rows - W, T - cand_rows)) + list(range(T - cand_rows, T))
-            self._graph_sel[gcap] = torch.tensor(rows, dtype=torch.int32, device=e.device)
+            self._graph_sel[gcap] = torch.tensor(shape.rows(), dtype=torch.int32, device=e.device)
             self._graph_splits[gcap] = e.n_splits_for(T, min(e.S_max, max(self.P + T, 1024)))
             self._graph_T[gcap] = T
-            # warm-up on a side stream (library handles, allocator), then restore the integer state;
-            # the K/V rows it wrote lie at >= P and are rewritten by the real step before being read
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._graph_body(gcap, forward_only)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            for t, sv in zip(state, saved):
-                t.copy_(sv)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._graph_logits[gcap] = self._graph_body(gcap, forward_only)
-            self._graphs[gcap] = g
+            self._graphs[gcap], self._graph_logits[gcap] = capture_step_graph(lambda: self._graph_body(shape, gcap, forward_only), state)
         torch.cuda.synchronize()
         st.record_host.zero_()              # the warm-up passes left records of the step number the first replay will produce: never mistake one for it
-        self._graph = "forward" if forward_only else "step"
-        self._graph_eos = (self.eos_set, self.controls is not None)        # the control VALUES live in device memory: no re-capture
-        self._graph_ctl = self.controls is not None          # what the body launches (and, sampling, which rows it returns) depends on it
-        self._graph_gen = e.generation
+        self._graph_key = self._graph_key_for(forward_only)
 
-    def _step_graph(self) -> dict:
-        e, st = self.e, self.st
-        if self._graph != "step" or self._graph_eos != (self.eos_set, self.controls is not None) or self._graph_gen != e.generation:
-            self._capture_graphs()
+    def _replay(self, forward_only: bool):
+        """A steady step as one graph launch: (re-)captures when the graphs are not those of _graph_key_for or the cache outgrew the
+        captured KV split count, replays the smallest bucket that holds the g candidates.  Returns (T, cand_rows, the body's rows)."""
+        e = self.e
+        if self._graph_key != self._graph_key_for(forward_only):
+            self._capture_graphs(forward_only=forward_only)
         gcap = self._bucket_for(self.g)
         T = self._graph_T[gcap]
         if abs(e.n_splits_for(T, self.P + T) - self._graph_splits[gcap]) >= 2:      # the cache outgrew the captured KV split count
-            self._capture_graphs()
+            self._capture_graphs(forward_only=forward_only)
         if self.P + T > e.S_max:
             raise cabi.LadeHipError(f"KV cache exhausted: P={self.P} + T={T} > S_max={e.S_max}")
-        P_before = self.P
         self._graphs[gcap].replay()
+        return T, gcap * self.gs, self._graph_logits[gcap]
+
+    def _polled_record(self) -> List[int]:
+        """The record of the step a replayed graph has just launched"""
+        st = self.st
         rec = st.poll_record(self._step_no + 1) if self.poll else None
         if rec is None:
             torch.cuda.current_stream().synchronize()
@@ -375,74 +476,45 @@ class LookaheadDecoder:
                 if rec is None:
                     rec = st.read_record()
                     self.poll = False
-                    self._graph = None
+                    self._graph_key = None
                     print("[lade] the step record did not arrive through the host-mapped buffer (absent even after the stream had drained): "
                           "falling back to stream synchronisation for this decoder", file=sys.stderr, flush=True)
             else:
                 rec = st.record_host.tolist()
-        self._step_no = rec[7]
-        self.steps += 1
-        max_hit, n_accept, eos_hit, self.g, self.P = rec[0], rec[1], rec[2], rec[3], rec[4]
-        accepted = rec[8:8 + n_accept]
-        self.tokens += accepted
-        self.finished_by_eos = bool(eos_hit)
-        return dict(T=T, P_before=P_before, n_input=1, max_hit=max_hit, max_hit_idx=rec[5], accepted=list(accepted),
-                    first_guess=rec[6], g_next=self.g, P_after=self.P, phase=2)
+        return rec
 
-    @torch.no_grad()
-    @_on_device
-    def step(self, keep_trace: bool = False) -> dict:
-        """One decode step = one model forward over T tokens + the device-side post-step; returns the
-        host-visible record (accepted tokens, max_hit ...)."""
-        e, st = self.e, self.st
-        W, N, G, gs = self.W, self.N, self.G, self.gs
-        prompt, P, g, fill_level = self.prompt, self.P, self.g, self.fill_level
-        if self.use_graph and self.steps > 0 and fill_level >= N - 2:
-            return self._step_graph()
-        if self.steps == 0:                                          # prefill: prompt + L0, plain causal
-            phase = 0
-            ids_h = prompt + self.window0
-            n_inp, cand_rows = len(self.window0), 0
-            # rows whose logits are read: the last prompt token and the window (:1578-1606)
-            prows = [len(prompt) - 1] + list(range(len(prompt), len(ids_h)))
-            logits, done = e.prefill(ids_h, prows)
-            T, P_before = len(ids_h) - done, done
-            n_input = len(prompt) - done                             # out row = last prompt token of the last chunk
-            if self.controls is not None:
-                self._gen_rows(logits, n_inp, self._prefill_pos(prows), None)
-                logits = None
-        else:
-            phase = 2 if fill_level >= N - 2 else 1
-            n_input = 1
-            ls = self._level_sizes(fill_level)
-            cand_rows = g * gs if phase == 2 else 0
-            mask = StepMask.from_levels(n_input, ls, cand_rows, gs, P)
-            T, P_before = mask.T, P
-            call("lade_build_inputs", None, None, n_input, ptr(st.window), st.wcap, ptr(st.ctl), min(fill_level, N - 2), 0, -1,
-                 ptr(st.guess), g if phase == 2 else 0, gs, cand_rows, ptr(st.ids), ptr(st.pos), None, 0, 1)
-            n_inp = ls[-1]
-            # rows whose logits are needed: out row, last level's rows, candidate rows (:1578-1606)
-            rows = [n_input - 1] + list(range(T - cand_rows - n_inp, T - cand_rows)) + list(range(T - cand_rows, T))
-            n_sel = self._set_sel(rows)
-            logits = e.forward(st.ids, st.pos, mask, st.sel, n_sel, argmax_out=None if self.controls is not None else st.am)
-            if self.controls is not None:
-                self._gen_rows(logits, n_inp, st.pos, st.sel)
-                logits = None
-        if logits is not None:                       # the prefill step returns its logits, a decode step has taken the argmax already
-            ops.argmax_rows(logits, out=st.am)
-        self._post_step(st.am, n_inp, T, cand_rows, phase)
-        ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
-        rec = st.read_record()
+    def _take_record(self, rec: List[int], phase: int) -> dict:
+        """A step's record into the host state; returns the fields every step's info carries"""
         self._step_no = rec[7]
         self.steps += 1
-        max_hit, n_accept, eos_hit, self.g, self.P = rec[0], rec[1], rec[2], rec[3], rec[4]
-        accepted = rec[8:8 + n_accept]
+        n_accept, eos_hit, self.g, self.P = rec[1], rec[2], rec[3], rec[4]
+        accepted = rec[8:8 + n_accept]                               # (sampling: = hits[:n_accept]; the record also carries a device-drawn token)
         self.tokens += accepted
         if phase != 2:
             self.fill_level += 1
         self.finished_by_eos = bool(eos_hit)
-        return dict(T=T, P_before=P_before, n_input=n_input, max_hit=max_hit, max_hit_idx=rec[5], accepted=list(accepted),
-                    first_guess=rec[6], g_next=self.g, P_after=self.P, phase=phase)
+        return dict(accepted=list(accepted), g_next=self.g, P_after=self.P, phase=phase)
+
+    def _steady_graph(self) -> bool:
+        return self.use_graph and self.steps > 0 and self.fill_level >= self.N - 2
+
+    @torch.no_grad()
+    @_on_device
+    def step(self) -> dict:
+        """One decode step = one model forward over T tokens + the device-side post-step; returns the
+        host-visible record (accepted tokens, max_hit ...)."""
+        e, st = self.e, self.st
+        if self._steady_graph():                                     # ONE graph launch, post-step included
+            phase, n_input, P_before = 2, 1, self.P
+            T, _, _ = self._replay(forward_only=False)
+            rec = self._polled_record()
+        else:
+            shape, T, P_before, _ = self._eager_model(want_rows=False)
+            phase, n_input = shape.phase, shape.n_input - (P_before if shape.phase == 0 else 0)      # prefill: out row = last prompt token of the last chunk
+            self._post_step(st.am, shape.n_inp, T, shape.cand_rows, phase)
+            ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
+            rec = st.read_record()
+        return dict(T=T, P_before=P_before, n_input=n_input, max_hit=rec[0], max_hit_idx=rec[5], first_guess=rec[6], **self._take_record(rec, phase))
 
     @torch.no_grad()
     @_on_device
@@ -461,31 +533,14 @@ class LookaheadDecoder:
                 raise cabi.LadeHipError(f"lookahead parallelism (DIST_WORKERS > 1 / FORCE_LP) stops on one EOS id only, got {list(eos)}: "
                                         "run on one GPU without FORCE_LP")
             from .parallel import greedy_lp
-            out = greedy_lp(self, prompt, max_length, eos[0] if eos else None, rng, keep_trace, on_step=on_step)
-            # the reference logs on rank 0 only (`if DEBUG and LOCAL_RANK == 0`, lade/decoding.py:1231-1235)
-            if CONFIG_MAP.get("DEBUG", 0) and self.lp.rank == 0:
-                CONFIG_MAP.setdefault("log", []).append([out.generated, out.steps, round(out.generated / max(out.steps, 1), 2)])
-            return out
+            return greedy_lp(self, prompt, max_length, eos[0] if eos else None, rng, keep_trace, on_step=on_step)
         self.start(prompt, eos_token_id, rng, controls)
-        trace: List[dict] = []
-        while True:
-            info = self.step()
-            if keep_trace:
-                trace.append(info)
-            if on_step is not None:
-                on_step(info["accepted"][:max(0, max_length - (len(self.tokens) - len(info["accepted"])))])
-            if self.finished_by_eos or len(self.tokens) >= max_length:      # stopping criteria (:1204-1219)
-                break
-        generated = min(len(self.tokens), max_length) - len(self.prompt)
-        out = GenOut(tokens=self.tokens[:max_length], steps=self.steps, generated=generated, trace=trace)
-        if CONFIG_MAP.get("DEBUG", 0):
-            CONFIG_MAP.setdefault("log", []).append([generated, self.steps, round(generated / self.steps, 2)])
-        return out
+        return generate_loop(self, self.step, max_length, keep_trace, on_step, log=True)
 
 
     # ---- sampling ------------------------------------------------------------------------------------
     def _sampling_buffers(self):
-        if getattr(self, "_smp", None) is None:
+        if self._smp is None:
             e, G, gs = self.e, max(self.G, 1), self.gs
             rows = 1 + G * gs
             dev = e.device
@@ -521,7 +576,7 @@ class LookaheadDecoder:
         e, W = self.e, self.W
         rng = rng if rng is not None else random
         self.start(prompt, eos_token_id, rng, controls)
-        if torch_gen is not None and torch_gen.device.type == "cuda" and not getattr(self, "_draw_warm", False):
+        if torch_gen is not None and torch_gen.device.type == "cuda" and not self._draw_warm:
             # the draw's torch kernels (exponential, divide, argmax, and the strike-and-renormalise ops of a rejected draft) load their code
             # objects on first use: 10-26 ms in the middle of the first step that rejects a draft.  One dry run on a throw-away generator -
             # the caller's generator is not touched
@@ -548,20 +603,7 @@ class LookaheadDecoder:
         `warp`: a sampling.Warper (temperature / top-k / top-p; temperature alone is applied inside the kernels) or any callable
         mapping fp32 logits rows [r, V] to warped logits (the HF warpers the reference admits, :375-377)."""
         self.sample_start(prompt, warp, eos_token_id, rng, torch_gen, controls)
-        trace: List[dict] = []
-        while True:
-            info = self.sample_step(keep_trace)
-            if keep_trace:
-                trace.append(info)
-            if on_step is not None:
-                on_step(info["accepted"][:max(0, max_length - (len(self.tokens) - len(info["accepted"])))])
-            if self.finished_by_eos or len(self.tokens) >= max_length:
-                break
-        generated = min(len(self.tokens), max_length) - len(self.prompt)
-        out = GenOut(tokens=self.tokens[:max_length], steps=self.steps, generated=generated, trace=trace)
-        if CONFIG_MAP.get("DEBUG", 0):
-            CONFIG_MAP.setdefault("log", []).append([generated, self.steps, round(generated / self.steps, 2)])
-        return out
+        return generate_loop(self, lambda: self.sample_step(keep_trace), max_length, keep_trace, on_step, log=True)
 
     @torch.no_grad()
     @_on_device
@@ -574,58 +616,20 @@ class LookaheadDecoder:
         S = self._s
         warp, fused_T, rng, torch_gen, all_old_tokens, forced, override = S["warp"], S["fused_T"], S["rng"], S["torch_gen"], S["old"], S["forced"], S["override"]
         buf = self._sampling_buffers()
-        prompt_l, P, g, fill_level = self.prompt, self.P, self.g, self.fill_level
-        P_before = P
-        if self.steps == 0:
-            phase = 0
-            ids_h = prompt_l + self.window0
-            n_inp, cand_rows = len(self.window0), 0
-            prows = [len(prompt_l) - 1] + list(range(len(prompt_l), len(ids_h)))
-            logits, done = e.prefill(ids_h, prows)
-            if self.controls is not None:
-                rows_out = torch.empty(1, e.V, dtype=torch.float32, device=e.device)
-                self._gen_rows(logits, n_inp, self._prefill_pos(prows), None, rows_out)
-                logits = rows_out
-            else:
-                logits = logits.float()
-                ops.argmax_rows(logits, out=st.am)
-            T, P_before = len(ids_h) - done, done
-        elif self.use_graph and fill_level >= N - 2:
+        g, fill_level = self.g, self.fill_level
+        if self._steady_graph():
             # steady step: input assembly + model step + argmax replayed as one hipGraph (candidate rows padded to the bucket)
             # controls on: the body returns the processed out / candidate rows (no window rows); off: logits.float() of every row
-            if self._graph != "forward" or self._graph_ctl != (self.controls is not None) or self._graph_gen != e.generation:
-                self._capture_graphs(forward_only=True)
-            phase, n_inp = 2, W
-            gcap = self._bucket_for(g)
-            T, cand_rows = self._graph_T[gcap], gcap * gs
-            if abs(e.n_splits_for(T, P + T) - self._graph_splits[gcap]) >= 2:
-                self._capture_graphs(forward_only=True)
-            if P + T > e.S_max:
-                raise cabi.LadeHipError(f"KV cache exhausted: P={P} + T={T} > S_max={e.S_max}")
-            self._graphs[gcap].replay()
-            logits = self._graph_logits[gcap]
+            phase, n_inp, P_before = 2, W, self.P
+            T, cand_rows, logits = self._replay(forward_only=True)
         else:
-            phase = 2 if fill_level >= N - 2 else 1
-            ls = self._level_sizes(fill_level)
-            cand_rows = g * gs if phase == 2 else 0
-            mask = StepMask.from_levels(1, ls, cand_rows, gs, P)
-            T = mask.T
-            call("lade_build_inputs", None, None, 1, ptr(st.window), st.wcap, ptr(st.ctl), min(fill_level, N - 2), 0, -1,
-                 ptr(st.guess), g if phase == 2 else 0, gs, cand_rows, ptr(st.ids), ptr(st.pos), None, 0, 1)
-            n_inp = ls[-1]
-            n_sel = self._set_sel([0] + list(range(T - cand_rows - n_inp, T - cand_rows)) + list(range(T - cand_rows, T)))
-            if self.controls is not None:
-                rows_out = torch.empty(1 + cand_rows, e.V, dtype=torch.float32, device=e.device)
-                self._gen_rows(e.forward(st.ids, st.pos, mask, st.sel, n_sel), n_inp, st.pos, st.sel, rows_out)
-                logits = rows_out
-            else:
-                logits = e.forward(st.ids, st.pos, mask, st.sel, n_sel).float()    # logits.float(), modeling_llama.py:1544
-                ops.argmax_rows(logits, out=st.am)                                    # window levels are filled by argmax (:459, :545)
+            shape, T, P_before, logits = self._eager_model(want_rows=True)
+            phase, n_inp, cand_rows = shape.phase, shape.n_inp, shape.cand_rows
         # generation controls: `logits` holds the processed fp32 out row and candidate rows only (lade_gen_rows), no window rows between
         n_skip = 0 if self.controls is not None else n_inp
         step_inputs = {}
         if keep_trace and phase != 0:                            # what the step fed and judged (tests re-derive the probabilities)
-            step_inputs = dict(ids=st.ids[:T].tolist(), pos=st.pos[:T].tolist(), level_sizes=list(self._level_sizes(fill_level)),
+            step_inputs = dict(ids=st.ids[:T].tolist(), pos=st.pos[:T].tolist(), level_sizes=level_sizes(W, N, fill_level),
                                cand_rows=cand_rows, g=g, drafts=st.guess[:g * gs].tolist() if phase == 2 else [])
         # ---- the step's token(s): rejection-sampling verify over the candidates, or a plain draw (:453-540) ----
         verify = phase == 2 and g > 0
@@ -675,15 +679,6 @@ class LookaheadDecoder:
             forced[2 + max_hit:3 + max_hit].copy_(drawn_on_device)          # the drawn token never left the device
         self._post_step(st.am, n_inp, T, cand_rows, phase, forced=forced, level_override=level_override)
         ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
-        rec = st.read_record()
-        self._step_no = rec[7]
-        self.steps += 1
-        n_accept, eos_hit, self.g, self.P = rec[1], rec[2], rec[3], rec[4]
-        accepted = rec[8:8 + n_accept]                                     # = hits[:n_accept]; the record also carries a device-drawn token
-        self.tokens += accepted
-        all_old_tokens += accepted
-        if phase != 2:
-            self.fill_level += 1
-        self.finished_by_eos = bool(eos_hit)
-        return dict(T=T, P_before=P_before, max_hit=max_hit, max_hit_idx=max_hit_idx, accepted=list(accepted), phase=phase, g_next=self.g,
-                    P_after=self.P, **step_inputs)
+        info = self._take_record(st.read_record(), phase)
+        all_old_tokens += info["accepted"]
+        return dict(T=T, P_before=P_before, max_hit=max_hit, max_hit_idx=max_hit_idx, **info, **step_inputs)

@@ -27,6 +27,8 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from .decoding import StepShape, capture_step_graph, generate_loop, step_shape
+
 REC_HEAD = 4           # first_guess, n_inp, g_local, (reserved)
 
 
@@ -180,6 +182,9 @@ class HipLPBackend:
         self.rec = torch.zeros(self.rw, dtype=torch.int32, device=dev)
         self.scratch = torch.zeros(dec.lp.R * st.wcap + dec.G * dec.gs + 64, dtype=torch.int32, device=dev)
         self.device = dev
+        self.prompt, self.window0, self.eos = [], [], -1       # of the current run (begin)
+        self.comm = None            # RcclComm when the step's collective goes through the C ABI (set by LPRunner)
+        self._segments = {}         # captured steady segments: (re-fed inputs, candidate bucket, engine generation) -> (graph, sel, n_splits)
 
     def begin(self, prompt: Sequence[int], window0: Sequence[int], eos: int) -> None:
         d = self.dec
@@ -188,39 +193,32 @@ class HipLPBackend:
         self.prompt = list(prompt)
         self.window0 = list(window0)
         self.eos = eos
+        d.controls = None            # lade_lp_reduce_apply knows no generation controls (LookaheadDecoder.greedy refuses them under LP)
         if d.pool_from_prompt:                                   # lade/decoding.py:915-916, on every rank
             pt = torch.tensor(self.prompt, dtype=torch.int32, device=self.device)
             self.call("lade_pool_fill_prompt", self.ptr(d.st.pool_tok), self.ptr(d.st.pool_cnt), d.st.V, d.G, d.gs, self.ptr(pt), len(self.prompt))
 
     def local_step(self, phase: int, P: int, n_input: int, level_lens: Sequence[int], c0: int, c1: int, g: int, glo: int, ghi: int):
         """Builds this rank's inputs, runs the forward, and packs its record (device tensor [rw])."""
-        from .ops import StepMask
-        d, st, e = self.dec, self.dec.st, self.dec.e
-        gs, N = d.gs, d.N
-        call, ptr = self.call, self.ptr
-        g_local = ghi - glo
-        cand_rows = g_local * gs if phase == 2 else 0
+        d, st = self.dec, self.dec.st
+        gs = d.gs
+        g_local = ghi - glo if phase == 2 else 0
         if phase == 0:
             # rank r prefills the prompt + the L0 prefix up to its last column (lade/decoding.py:981-984)
-            ids_h = self.prompt + self.window0[: c1 - 1]
-            n_inp = c1 - 1
-            logits, done = e.prefill(ids_h, [len(self.prompt) - 1] + list(range(len(self.prompt), len(ids_h))))
-        else:
-            ls = shard_level_sizes(level_lens, c0, c1)
-            mask = StepMask.from_levels(n_input, ls, cand_rows, gs, P)
-            T = mask.T
-            guess_ptr = st.guess.data_ptr() + 4 * glo * gs
-            call("lade_build_inputs", None, None, n_input, ptr(st.window), st.wcap, ptr(st.ctl), len(level_lens) - 1, c0, c1,
-                 guess_ptr, g_local if phase == 2 else 0, gs, cand_rows, ptr(st.ids), ptr(st.pos), None, 0, 1)
-            n_inp = ls[-1]
-            rows = [n_input - 1] + list(range(T - cand_rows - n_inp, T - cand_rows)) + list(range(T - cand_rows, T))
-            d._set_sel(rows)                 # cached on the device per shape: no host-to-device copy in a steady step
-            logits = e.forward(st.ids, st.pos, mask, st.sel, len(rows), argmax_out=st.am)
-        if logits is not None:
+            shape = StepShape(0, len(self.prompt), (c1 - 1,), 0)
+            logits, done = d.e.prefill(self.prompt + self.window0[: c1 - 1], shape.rows())
             self.ops.argmax_rows(logits, out=st.am)
-        am = st.am.data_ptr()
-        call("lade_lp_pack", am, am + 4, n_inp, am + 4 * (1 + n_inp), g_local if phase == 2 else 0, gs, st.wcap, ptr(self.rec), self.rw, None, 0, 1)
+        else:
+            shape = StepShape(phase, n_input, tuple(shard_level_sizes(level_lens, c0, c1)), g_local * gs)
+            d._model_step(shape, False, P, g_local, None, c0, c1, guess=st.guess.data_ptr() + 4 * glo * gs)
+        self._pack(shape.n_inp, g_local)
         return self.rec
+
+    def _pack(self, n_inp: int, g: int, ctl=None, lp=(0, 1)) -> None:
+        """st.am [out | n_inp window | candidates] into this rank's record"""
+        st = self.dec.st
+        am = st.am.data_ptr()
+        self.call("lade_lp_pack", am, am + 4, n_inp, am + 4 * (1 + n_inp), g, self.dec.gs, st.wcap, self.ptr(self.rec), self.rw, self.ptr(ctl), *lp)
 
     # ---- steady step as a hipGraph segment: [input assembly -> forward -> argmax -> record] ---------------------------------------
     # Fixed shapes per (re-fed input count, candidate bucket): the rank's candidate share is decided on the device from ctl[G]
@@ -233,66 +231,43 @@ class HipLPBackend:
         gl = (self.dec.G + self.dec.lp.R - 1) // self.dec.lp.R
         return sorted({0, (gl + 1) // 2, gl})
 
-    def _segment_body(self, n_input: int, ls: Sequence[int], c0: int, c1: int, gcap: int, sel: torch.Tensor, n_splits: int):
-        from .ops import StepMask
-        d, st, e = self.dec, self.dec.st, self.dec.e
-        gs, lp = d.gs, d.lp
-        call, ptr = self.call, self.ptr
-        cand_rows = gcap * gs
-        mask = StepMask.from_levels(n_input, ls, cand_rows, gs, 0)
-        call("lade_build_inputs", None, None, n_input, ptr(st.window), st.wcap, ptr(st.ctl), d.N - 2, c0, c1, ptr(st.guess), -1, gs, cand_rows,
-             ptr(st.ids), ptr(st.pos), None, lp.rank, lp.R)
-        e.forward(st.ids, st.pos, mask, sel, sel.numel(), dyn_P=st.ctl, n_splits=n_splits, argmax_out=st.am)
-        am = st.am.data_ptr()
-        n_inp = ls[-1]
-        call("lade_lp_pack", am, am + 4, n_inp, am + 4 * (1 + n_inp), gcap, gs, st.wcap, ptr(self.rec), self.rw, ptr(st.ctl), lp.rank, lp.R)
+    def _segment_body(self, shape: StepShape, c0: int, c1: int, sel: torch.Tensor, n_splits: int):
+        d, st, lp = self.dec, self.dec.st, self.dec.lp
+        d._model_step(shape, False, 0, -1, sel, c0, c1, lp=(lp.rank, lp.R), dyn_P=st.ctl, n_splits=n_splits)
+        self._pack(shape.n_inp, shape.cand_rows // d.gs, st.ctl, (lp.rank, lp.R))
 
-    def _capture_segment(self, P: int, n_input: int, ls: Sequence[int], c0: int, c1: int, gcap: int):
-        d, st, e = self.dec, self.dec.st, self.dec.e
-        gs = d.gs
-        T = n_input + sum(ls) + gcap * gs
-        rows = [n_input - 1] + list(range(T - gcap * gs - ls[-1], T))
-        sel = torch.tensor(rows, dtype=torch.int32, device=self.device)
-        n_splits = e.n_splits_for(T, max(P + T, 1024))
+    def _capture_segment(self, P: int, shape: StepShape, c0: int, c1: int):
+        st, e = self.dec.st, self.dec.e
+        sel = torch.tensor(shape.rows(), dtype=torch.int32, device=self.device)
+        n_splits = e.n_splits_for(shape.T, max(P + shape.T, 1024))
         state = (st.ctl, st.window, st.pool_cnt, st.pool_tok, st.guess, st.tail)
-        with HipLPBackend._capture_lock:           # one capture at a time per process (ranks may be threads in the tests)
-            saved = [t.clone() for t in state]
-            try:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    self._segment_body(n_input, ls, c0, c1, gcap, sel, n_splits)       # warm-up: library handles, autotune
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-            finally:                                   # whatever the warm-up did to the integer state is undone - also when it failed (LPRunner falls back to eager steps)
-                for t, sv in zip(state, saved):
-                    t.copy_(sv)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._segment_body(n_input, ls, c0, c1, gcap, sel, n_splits)
+        # one capture at a time per process (ranks may be threads in the tests).  Whatever the warm-up did to the integer state is undone
+        # also when it failed (LPRunner falls back to eager steps)
+        with HipLPBackend._capture_lock:
+            g, _ = capture_step_graph(lambda: self._segment_body(shape, c0, c1, sel, n_splits), state, capture_error_mode="thread_local")
         return (g, sel, n_splits)
 
     def local_step_graph(self, P: int, n_input: int, level_lens: Sequence[int], c0: int, c1: int, g_local: int):
         """Replays (capturing on first use) the segment for this step's shape; returns the record tensor.  The first steady step
         (one input token) captures the segments of ALL candidate buckets at once, like the single-GPU decoder does: the GEMM autotune
         of a wider row class then happens during warm-up, not in the step that first meets a candidate."""
-        d, st, e = self.dec, self.dec.st, self.dec.e
-        gs = d.gs
-        ls = shard_level_sizes(level_lens, c0, c1)
+        e, gs = self.dec.e, self.dec.gs
         gcap = min(b for b in self._local_buckets() if b >= g_local)
-        T = n_input + sum(ls) + gcap * gs
+        shape = StepShape(2, n_input, tuple(shard_level_sizes(level_lens, c0, c1)), gcap * gs)
+        T = shape.T
         if P + T > e.S_max:
             raise self.dec_error(f"KV cache exhausted: P={P} + T={T} > S_max={e.S_max}")
         key = (n_input, gcap, e.generation)
-        graphs = self.__dict__.setdefault("_segments", {})
+        graphs = self._segments
         want_splits = e.n_splits_for(T, P + T)
         ent = graphs.get(key)
         if ent is None or abs(want_splits - ent[2]) >= 2:
-            ent = graphs[key] = self._capture_segment(P, n_input, ls, c0, c1, gcap)
+            ent = graphs[key] = self._capture_segment(P, shape, c0, c1)
             if n_input == 1:
                 for b in self._local_buckets():
-                    if (1, b, e.generation) not in graphs and P + 1 + sum(ls) + b * gs <= e.S_max:
-                        graphs[(1, b, e.generation)] = self._capture_segment(P, 1, ls, c0, c1, b)
+                    other = StepShape(2, 1, shape.level_sizes, b * gs)
+                    if (1, b, e.generation) not in graphs and P + other.T <= e.S_max:
+                        graphs[(1, b, e.generation)] = self._capture_segment(P, other, c0, c1)
         ent[0].replay()
         return self.rec
 
@@ -310,8 +285,6 @@ class HipLPBackend:
 
     def new_gather_buffer(self, R: int) -> torch.Tensor:
         return torch.zeros(R * self.rw, dtype=torch.int32, device=self.device)
-
-    comm = None          # RcclComm when the step's collective goes through the C ABI (set by LPRunner)
 
     def broadcast_window(self, window0: List[int], lp: LPContext) -> List[int]:
         """rank 0's random window reaches every rank (lade/decoding.py:905-906)"""
@@ -360,8 +333,8 @@ class LPRunner:
     def __init__(self, dec, backend=None, all_gather=None, comm: Optional[RcclComm] = None):
         self.dec = dec
         self.lp: LPContext = dec.lp
+        self.comm = comm
         if comm is not None:                 # a communicator the caller built over its own channel (no torch.distributed involved)
-            self.comm = comm
             all_gather = comm.all_gather
         # the collective is injectable so that tests can run several ranks inside one process.  Default: torch.distributed's
         # all_gather_into_tensor (RCCL); LADE_LP_COLLECTIVE=abi routes it through the C ABI's own communicator
@@ -382,7 +355,7 @@ class LPRunner:
         if self.lp.R > self.W:
             raise ValueError(f"lookahead parallelism needs DIST_WORKERS ({self.lp.R}) <= WINDOW_SIZE ({self.W})")
         self.be = backend if backend is not None else HipLPBackend(dec)
-        if getattr(self, "comm", None) is not None:
+        if self.comm is not None:
             self.be.comm = self.comm
 
     def start(self, prompt: Sequence[int], eos_token_id: Optional[int] = None, rng: Optional[random.Random] = None) -> None:
@@ -396,20 +369,13 @@ class LPRunner:
         self.be.begin(self.prompt, window0, self.eos)
         self.all_rec = self.be.new_gather_buffer(self.lp.R)
         self.tokens = list(self.prompt)
-        self.steps, self.P, self.g, self.fill_level, self.n_input = 0, 0, 0, 0, len(self.prompt)
-        self.finished = False
+        self.steps, self.P, self.g, self.n_input = 0, 0, 0, len(self.prompt)
+        self.finished_by_eos = False
 
     def step(self) -> dict:
         W, N, R, r = self.W, self.N, self.lp.R, self.lp.rank
-        fill_level = self.fill_level
-        phase = 0 if self.steps == 0 else (2 if fill_level >= N - 2 else 1)
-        # level lengths before this step (see LookaheadDecoder._level_sizes)
-        if fill_level == 0:
-            level_lens = [W + N - 3]
-        elif fill_level >= N - 2:
-            level_lens = [W - 1] + [W] * (N - 2)
-        else:
-            level_lens = [W + N - 3 - fill_level] + [W + N - 2 - fill_level] * fill_level
+        shape = step_shape(W, N, self.steps, self.g, self.n_input)      # of the whole step; the rank feeds its shard of it
+        phase, level_lens = shape.phase, shape.level_sizes
         c0, c1 = window_shard(level_lens[0] + 1, R, r)
         glo, ghi = guess_shard(self.g, R, r) if phase == 2 else (0, 0)
         # (dynamic-NTK RoPE: a padded graph segment would count its padding as sequence length - those models take the eager LP step)
@@ -436,11 +402,9 @@ class LPRunner:
         # EOS scan (lade/decoding.py:1167-1177): the reference keeps everything up to and including EOS
         if self.eos >= 0 and self.eos in accepted:
             accepted = accepted[:accepted.index(self.eos) + 1]
-            self.finished = True
+            self.finished_by_eos = True
         self.tokens += accepted
         self.n_input = 1 + max_hit                                           # re-feed the hits (:1148-1153)
-        if phase != 2:
-            self.fill_level += 1
         return dict(phase=phase, max_hit=max_hit, accepted=list(accepted), c0=c0, c1=c1, glo=glo, ghi=ghi, P_after=self.P, g_next=self.g,
                     T=None)
 
@@ -449,17 +413,7 @@ def greedy_lp(dec, prompt: Sequence[int], max_length: int, eos_token_id: Optiona
               rng: Optional[random.Random] = None, keep_trace: bool = False, backend=None, all_gather=None, on_step=None, comm=None):
     """Greedy lookahead decoding under lookahead parallelism (jacobi_greedy_search_multilevel with
     DIST_WORKERS > 1, lade/decoding.py:697-1259)."""
-    from .decoding import GenOut
     run = LPRunner(dec, backend, all_gather, comm=comm)
     run.start(prompt, eos_token_id, rng)
-    trace: List[dict] = []
-    while True:
-        info = run.step()
-        if keep_trace:
-            trace.append(info)
-        if on_step is not None:
-            on_step(info["accepted"][:max(0, max_length - (len(run.tokens) - len(info["accepted"])))])
-        if run.finished or len(run.tokens) >= max_length:
-            break
-    generated = min(len(run.tokens), max_length) - len(run.prompt)
-    return GenOut(tokens=run.tokens[:max_length], steps=run.steps, generated=generated, trace=trace)
+    # the reference logs on rank 0 only (`if DEBUG and LOCAL_RANK == 0`, lade/decoding.py:1231-1235)
+    return generate_loop(run, run.step, max_length, keep_trace, on_step, log=dec.lp.rank == 0)

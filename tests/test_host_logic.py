@@ -198,6 +198,34 @@ def test_graph_buckets_follow_the_gemm_row_classes():
     assert buckets(15, 5, 15) == [0, 1, 4, 9, 15] and buckets(20, 7, 20) == [0, 1, 5, 6, 12, 20]
 
 
+def test_step_shape_matches_every_step_of_the_reference_traces():
+    """decoding.step_shape / StepShape (plain host arithmetic: no device, no decoder): phase, level sizes, candidate rows, T and the
+    logits-row selection of every step of the reference's own greedy, sampling and dynamic-NTK runs."""
+    import json
+    import os
+    from conftest import GOLDEN
+    from lookaheaddecoding_amd.decoding import step_shape
+    n = 0
+    for name in ("e2e_greedy.json", "e2e_greedy_wide.json", "e2e_unlimited.json", "e2e_sample.json", "e2e_sample_eos.json", "e2e_dynamic_ntk.json"):
+        with open(os.path.join(GOLDEN, name)) as f:
+            runs = json.load(f)["runs"]
+        for run in runs:
+            W, N = run["W"], run["N"]
+            for i, tr in enumerate(run["trace"]):
+                ls, lg, ni = tr["level_sizes"], tr["lguess"], tr["n_input"]
+                assert lg % (N - 1) == 0
+                shape = step_shape(W, N, i, lg // (N - 1), ni)
+                assert list(shape.level_sizes) == ls and shape.cand_rows == lg and shape.n_inp == ls[-1], (name, i)
+                assert (shape.phase == 0) == (i == 0) and shape.phase == (0 if i == 0 else 2 if len(ls) == N - 1 else 1), (name, i)
+                if i > 0:
+                    assert shape.T == ni + sum(ls) + lg == len(tr["ids"]), (name, i)
+                rows = shape.rows()
+                assert len(rows) == 1 + ls[-1] + lg and all(a < b for a, b in zip(rows, rows[1:])) and rows[-1] == shape.T - 1, (name, i)
+                assert rows[0] == ni - 1
+                n += 1
+    assert n >= 700
+
+
 def test_rendezvous_ports_are_picked_below_the_ephemeral_range():
     """conftest.free_port: a port the kernel cannot hand to an outgoing connection between the probe and the TCPStore's bind (the diagnosed
     cause of the 1-in-50 start-up stall: EADDRINUSE at rank 0, the other ranks waiting for a store that never comes)."""
