@@ -17,6 +17,7 @@
  *                            lade/models/modeling_llama.py:705-713 (flash) and the eager op
  *                            :520-541 + the dense mask of :115-207 (evaluated in-kernel here)
  *   lade_attn_combine        (second pass of the split-KV attention; no reference counterpart)
+ *   lade_attn_prefill        eager attention under the causal prefill mask (modeling_llama.py:124-130, :520-541), chunks > 256 rows
  *   lade_rope_kv_append      apply_rotary_pos_emb + torch.cat KV append
  *                            lade/models/modeling_llama.py:321-346, :510-516
  *   lade_kv_commit           lade/decoding.py:1154-1163 (greedy) / :582-590 (sample)
@@ -172,6 +173,20 @@ typedef struct lade_attn_args {
 int lade_attn_fwd(const lade_attn_args* a, void* stream);
 /* merges the n_splits partials of lade_attn_fwd into `out` (call only when n_splits > 1) */
 int lade_attn_combine(const lade_attn_args* a, void* stream);
+/* One-pass causal attention for a prefill chunk (replaces the reference's eager attention under the plain causal mask of a prompt:
+ * lade/models/modeling_llama.py:124-130 build the mask, :520-541 apply it).  lade_attn_fwd is built for the decode step (few rows, long
+ * cache, HBM bound: KV splits + lade_attn_combine); this entry point is the compute-bound form for chunks of hundreds to thousands of rows:
+ * work-groups of 8 waves x 32 query rows, every K / V^T tile staged once per 256 rows, tiles above a block's diagonal never requested,
+ * longest blocks first, ONE launch and no partial buffers.
+ * The engine launches it only under LADE_DEBUG=prefill_attn=1.
+ * Takes lade_attn_args as it is and requires: mask.is_prefill == 1 (row t of the chunk sees keys 0 .. P + t), n_parts == 0, sync_flags == NULL,
+ * dyn_P == NULL, dtype LADE_BF16 or LADE_F16, d = 64 or 128, S_max a multiple of 64 (at most 2^22) and >= P + T, q / out 16-byte aligned with
+ * row strides that are multiples of 8 elements (q may be a view into the qkv buffer).  Anything else returns LADE_E_ARG with a message.
+ * Reads k_cache [Hkv][S_max][d] and vt_cache [Hkv][d][S_max] (rows P .. P+T already appended), writes out [T][H][d].  n_splits, wg_rows,
+ * part_o and part_ml are ignored.  Scores stay fp32, the softmax is online in the log2 domain, P is rounded to the model dtype before PV
+ *  - the arithmetic of lade_attn_fwd's 128-row shape, operation for operation: the output equals lade_attn_fwd's with
+ * n_splits = 1 bit for bit.  Cache rows at and beyond P + T may hold anything (NaN included): they never reach the output. */
+int lade_attn_prefill(const lade_attn_args* a, void* stream);
 /* dense 0/1 rendering of the mask predicate, [T][P+T] bytes on the device (test / debug aid) */
 int lade_mask_render(const lade_mask_params* m, uint8_t* out, void* stream);
 

@@ -76,6 +76,7 @@ _i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 SIGNATURES = {
     "lade_attn_fwd": [C.POINTER(AttnArgs), _vp],
     "lade_attn_combine": [C.POINTER(AttnArgs), _vp],
+    "lade_attn_prefill": [C.POINTER(AttnArgs), _vp],
     "lade_mask_render": [C.POINTER(MaskParams), _vp, _vp],
     "lade_rope_kv_append": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "lade_rope_rows_dynamic": [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp],

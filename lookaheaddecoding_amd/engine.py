@@ -96,7 +96,7 @@ def _on_device(fn):
     return wrapped
 
 
-from .tuning import (KernelDecisions, REP_ROWS, _STEP_TUNE_CACHE, _STEP_TUNE_LOCK, _TUNE_CACHE, _TUNE_LOCK, _TUNE_RANKED, _TUNE_TIMES,  # noqa: F401 (re-exported: tests / tools)
+from .tuning import (KernelDecisions, use_prefill_attn, REP_ROWS, _STEP_TUNE_CACHE, _STEP_TUNE_LOCK, _TUNE_CACHE, _TUNE_LOCK, _TUNE_RANKED, _TUNE_TIMES,  # noqa: F401 (re-exported: tests / tools)
                      gpu_identity, shipped_tune_table)
 
 
@@ -481,6 +481,8 @@ class StepEngine(KernelDecisions):
             acfg = (0,) + tuple(acfg[1:])
         if n_splits is None:
             n_splits = self.n_splits_for(T, P + T, choice=acfg if fused else None)
+        # causal chunks above the last row class (the ones on the library GEMMs): the one-pass prefill kernel instead of the split-KV pair
+        pf_attn = use_prefill_attn(T, mask.is_prefill, self.dtype, self.ROW_CLASSES[-1], dyn_P=dyn_P is not None, H=H, Hkv=Hkv, n_cu=self.n_cu)
         fuse_rope = bool(acfg[0]) and cfg_qkv is not None and cfg_qkv[2] <= 4 and not self.skip_attn
         fuse_embed = cabi.debug("fuse_tail", "1") != "0"      # embedding lookup inside the first layer's input norm (one launch less)
         if not (fuse_embed and self.layers):
@@ -535,13 +537,16 @@ class StepEngine(KernelDecisions):
                 ops.attn_fwd(qb if prod else None, self.k_cache(li), self.vt_cache(li), mask, H=H, Hkv=Hkv, d=d, out=o, n_splits=n_splits, part_o=self.part_o,
                              part_ml=self.part_ml, dyn_P=dyn_P, wg_rows=acfg[1], qkv_parts=part, n_parts=cfg_qkv[2], positions=rpos, cos=rcos, sin=rsin,
                              sync_flags=self.attn_flags if prod else None)
+            elif not self.skip_attn and pf_attn:
+                # one launch, no partials, no merge: the kernel has no KV split, so `n_splits` (a caller's, or LADE_DEBUG=attn_splits) does not apply
+                ops.attn_prefill(q_in, self.k_cache(li), self.vt_cache(li), mask, H=H, Hkv=Hkv, d=d, out=o)
             elif not self.skip_attn:
                 ops.attn_fwd(q_in, self.k_cache(li), self.vt_cache(li), mask, H=H, Hkv=Hkv, d=d, out=o, n_splits=n_splits,
                              part_o=self.part_o, part_ml=self.part_ml, dyn_P=dyn_P, wg_rows=acfg[1])
             if ev is not None:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()
-                ev.append((e0, e1, mask.T, n_splits))
+                ev.append((e0, e1, mask.T, 0 if pf_attn else n_splits))       # 0 splits = the one-pass prefill kernel ran
             if cfg_o:
                 ops.gemm_parts(o, self._w(lw, "wo"), part, cfg_o[2], cfg_o[1], cfg_o[0], cfg_o[3], cfg_o[4], cfg_o[5])
                 ops.add_rmsnorm_parts(x, part, cfg_o[2], lw["ln2"], self.eps, out=h)      # x += attn; h = norm(x)

@@ -157,6 +157,36 @@ def attn_fwd(q: Optional[torch.Tensor], k_cache: torch.Tensor, vt_cache: torch.T
     return out
 
 
+PREFILL_ATTN_CALLS = 0      # launches of lade_attn_prefill by this process (tests assert that the entry point was reached, or was not)
+
+
+def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor, vt_cache: torch.Tensor, mask: StepMask, *, H: int, Hkv: int, d: int,
+                 out: Optional[torch.Tensor] = None, scale: Optional[float] = None, q_row_stride: Optional[int] = None) -> torch.Tensor:
+    """One-pass causal attention of a prefill chunk (lade_attn_prefill: bf16 / f16, d = 64 | 128, mask.is_prefill): row t sees keys 0 .. P + t.
+    q: [T, >= H*d] rows (token stride q_row_stride elements, default q.stride(0): a view into the qkv buffer is fine); k_cache [Hkv, S_max, d];
+    vt_cache [Hkv, d, S_max] with the chunk's rows P .. P+T already appended; returns out [T, H*d].  One launch, no partial buffers.
+    What the library refuses (fp32, lookahead masks, other head sizes) raises LadeHipError: there is no fall-back to lade_attn_fwd here -
+    the caller decides which kernel a step runs on (tuning.use_prefill_attn)."""
+    global PREFILL_ATTN_CALLS
+    for n, t in (("q", q), ("k_cache", k_cache), ("vt_cache", vt_cache)):
+        _dev(t, n)
+    T = mask.T
+    S_max = k_cache.shape[1]
+    assert k_cache.shape == (Hkv, S_max, d) and vt_cache.shape == (Hkv, d, S_max), (k_cache.shape, vt_cache.shape)
+    assert k_cache.is_contiguous() and vt_cache.is_contiguous()
+    dt = k_cache.dtype
+    assert q.stride(-1) == 1 and q.dtype == dt
+    if out is None:
+        out = torch.empty(T, H * d, dtype=dt, device=k_cache.device)
+    assert out.dtype == dt and out.dim() == 2 and out.shape[0] >= T and out.shape[1] == H * d and out.stride(-1) == 1 and q.shape[0] >= T, (out.shape, out.dtype)
+    a = AttnArgs(ptr(q), ptr(k_cache), ptr(vt_cache), ptr(out), None, None, None,
+                 q_row_stride if q_row_stride is not None else q.stride(0), out.stride(0), H, Hkv, d, S_max,
+                 DTYPE_CODE_OF(dt), 1, scale if scale is not None else 1.0 / math.sqrt(d), mask.c_struct(), 0)
+    call("lade_attn_prefill", C.byref(a))
+    PREFILL_ATTN_CALLS += 1
+    return out
+
+
 def DTYPE_CODE_OF(dt: torch.dtype) -> int:
     try:
         return cabi.DTYPE_CODE[dt]

@@ -40,6 +40,45 @@ _STEP_TUNE_LOCK = __import__("threading").Lock()
 REP_ROWS = {32: 30, 64: 60, 96: 92, 128: 128, 160: 156, 192: 180, 256: 240}        # the rows a row class is timed at
 
 
+PREFILL_ATTN_WG_ROWS = 256       # query rows of the (head-in-group, token) row space per work-group of lade_attn_prefill (csrc/attn_prefill.hip)
+
+
+def prefill_attn_grid(T: int, H: int, Hkv: int) -> int:
+    """work-groups of one lade_attn_prefill launch: 256-row blocks of the n_rep x T rows of a KV head, times KV heads (no KV split)"""
+    return -(-(H // Hkv) * T // PREFILL_ATTN_WG_ROWS) * Hkv
+
+
+def use_prefill_attn(T: int, is_prefill: bool, dtype, last_row_class: int = 256, switch: Optional[str] = None, dyn_P: bool = False,
+                     H: int = 0, Hkv: int = 0, n_cu: int = 256) -> bool:
+    """Which attention kernel a step launches: True = the one-pass causal kernel (lade_attn_prefill), False = the split-KV pair
+    (lade_attn_fwd + lade_attn_combine).  The one-pass kernel takes the plain causal chunks in bf16 / f16 whose row count is above the last
+    GEMM row class - exactly the chunks that run on the library GEMMs; one-token steps, lookahead steps, causal chunks of up to
+    `last_row_class` rows, fp32 and steps that read the cache length from the device stay where they were (existing bit-exact comparisons
+    between engines are on those).
+    H, Hkv given: the chunk must also give the one-pass kernel enough work-groups.  It has no KV split, so a chunk whose 256-row blocks do
+    not cover the chip's CUs runs on part of the chip while the split-KV kernel fills it with splits: measured slower there
+    (profiles/prefill_attn_bench.txt: 512 rows on the 7B heads = 64 work-groups, 1.03 x the pair's time at P = 0; 512 rows on the 70B heads
+    = 128 work-groups, 1.16 x).  Such chunks stay on the pair.  One exception, a DELIBERATE LOSS: chunks for which even the pair's 128-row
+    blocks number at most an eighth of the CUs (models of two or three heads, i.e. the parity shapes tiny-d128 / tiny-d64) run on the
+    one-pass kernel although it is 1.1-4.5 x slower per launch there (profiles/prefill_attn_bench_small_models.txt: tens of microseconds),
+    so that the engine path through the kernel is exercised by the small-model parity tests; a model of 4 heads or more never takes it.
+    NOT THE DEFAULT: the kernel is behind LADE_DEBUG=prefill_attn=1.  The issue that asked for it set a bar for the default - at most 0.80 x the
+    pair's time at 2048 rows on >= 6144 keys, 7B and 70B heads - and the kernel's shipped (two-state, bit-identical) form has not been measured
+    against it; without the switch every step launches what it launched before.
+    switch: the value of LADE_DEBUG=prefill_attn (None: read it) - "1" routes the chunks described above to the one-pass kernel, anything
+    else (and no switch at all) leaves them on the split-KV pair; the two arms of tools/prefill_attn_bench.py and tools/prefill_rate_ab.py."""
+    if switch is None:
+        switch = cabi.debug("prefill_attn", "0")
+    if str(switch) != "1":
+        return False
+    if not (bool(is_prefill) and not dyn_P and dtype in (torch.bfloat16, torch.float16) and T > last_row_class):
+        return False
+    if H and Hkv:
+        pair_blocks = -(-(H // Hkv) * T // 128) * Hkv
+        return prefill_attn_grid(T, H, Hkv) >= n_cu or pair_blocks <= n_cu // 8
+    return True
+
+
 class KernelDecisions:
     """mixin of StepEngine: kernel decisions per (projection | attention launch, row class)"""
 
