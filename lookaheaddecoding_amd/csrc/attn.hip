@@ -22,7 +22,7 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "attn_core.hpp"
 
 // Cache policy of the K / V stream (bits 1 = sc0, 2 = nt, 16 = sc1), a COMPILE-time constant: NON-TEMPORAL + sc1 since round 6.  The cache of a 2 k-token sequence
 // is 1 GB per 7B model - far beyond L2 and the Infinity Cache - and every step reads all of it once: at the default policy it only evicts what IS re-read
@@ -39,16 +39,6 @@
 #endif
 
 namespace lade {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int KT = 64;        // keys per tile
-constexpr float NEG_BIG = -1.0e30f;     // initial running max
-constexpr float MASKED = -3.0e30f;      // masked score: 2^(MASKED - m) == 0 even while m is still NEG_BIG
 
 struct AttnK {
     const uint16_t* q;
@@ -186,37 +176,6 @@ __global__ void mask_render_kernel(lade_mask_params m, uint8_t* out) {
     }
 }
 
-// ---- LDS tiles ------------------------------------------------------------------------------
-// K tile [KT keys][D] and V^T tile [D][KT keys] are filled by LDS-DMA (global_load_lds, 16 B per
-// lane, no VGPR staging).  The DMA writes LDS linearly (wave-uniform base + lane*16), so the XOR
-// swizzle that keeps the ds_read_b128 fragment reads conflict-free is applied to the per-lane
-// SOURCE address and to the read address (never to the destination).
-template <int ROW_BYTES>
-__device__ __forceinline__ int swz16(int row) {          // 16-B chunk swizzle of a row-major tile
-    constexpr int CPR = ROW_BYTES / 16;                  // chunks per row
-    constexpr int RPB = 256 / ROW_BYTES > 0 ? 256 / ROW_BYTES : 1;   // rows per 256-B bank row
-    return (row / RPB) & (CPR - 1);
-}
-template <int ROW_BYTES>
-__device__ __forceinline__ int tile_off(int row, int c16) { return row * ROW_BYTES + ((c16 ^ swz16<ROW_BYTES>(row)) << 4); }
-
-// MFMA row index rho (0..31) of an S^T sub-tile <-> key kappa within the sub-tile.  With
-// kappa = (rho&3) | ((rho>>3)&3)<<2 | ((rho>>2)&1)<<4 the 16 S^T values a lane holds are the 16
-// CONTIGUOUS keys 16*hi .. 16*hi+15, so each PV k-step needs 8 contiguous keys of V^T = one 16-B read.
-__device__ __forceinline__ int kappa(int rho) { return (rho & 3) | (((rho >> 3) & 3) << 2) | (((rho >> 2) & 1) << 4); }
-
-template <typename T> struct Mfma;
-template <> struct Mfma<BF16> {
-    __device__ static __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mfma<F16> {
-    __device__ static __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-
 // ---- merge of split-KV partials (shared by the in-launch merge and lade_attn_combine: identical arithmetic, identical results) ----
 // out = sum_s w_s o_s / sum_s w_s with w_s = l_s 2^(m_s - m); o_s = normalised per-split outputs in the model dtype.  One call merges
 // 16 bytes (8 values) of one (token, head); splits are taken 8 at a time and ALL loads of a group are requested before the first use.
@@ -276,8 +235,6 @@ struct PlainPartials {
     __device__ __forceinline__ u32x4 po(int s) const { return *reinterpret_cast<const u32x4*>(po_p + s * po_stride); }
 };
 
-constexpr float RESCALE_THR = 8.0f;    // log2 units: the running max is only raised when it grows by more
-
 // optional in-kernel timeline (build with -DLADE_ATTN_TIMELINE, run with LADE_DEBUG=attn_dbg=16): thread 0 of every
 // work-group stamps s_memtime at 7 points into the words that follow part_ml
 #ifdef LADE_ATTN_TIMELINE
@@ -292,13 +249,6 @@ __device__ __forceinline__ void dbg_stamp(const AttnK& a, int slot) {
 #else
 __device__ __forceinline__ void dbg_stamp(const AttnK&, int) {}
 #endif
-
-// Work-group barrier that the compiler cannot move memory operations across.  The raw
-// __builtin_amdgcn_s_barrier() is IntrNoMem: LDS reads that follow it in the source may be scheduled
-// BEFORE it (observed: Q fragments read ahead of the barrier that publishes other waves' LDS-DMA).
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_barrier" ::: "memory"); }
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // ---- fused RoPE + KV append ------------------------------------------------------------------------------------------------------
 // The qkv projection of a decode step is a split-K GEMM that leaves fp32 partials; round 1-4 summed them, rotated q / k and appended the
@@ -468,12 +418,11 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
     constexpr int DBLK = D / 32;                   // 32-row blocks of O^T
     constexpr int K_BYTES = KT * D * 2, V_BYTES = D * KT * 2, TILE_BYTES = K_BYTES + V_BYTES, STAGE_BYTES = TPS * TILE_BYTES;
     constexpr int Q_BYTES = ROWS * D * 2;
-    constexpr int KPW = K_BYTES / 1024 / NW;       // 1-KiB DMA pieces per wave per tile
-    constexpr int VPW = V_BYTES / 1024 / NW;
-    constexpr int QPW = Q_BYTES / 1024 / NW;
-    constexpr int PIECES = TPS * (KPW + VPW);      // per wave per stage
+    using Stream = KvStream<D, NW>;                // this wave's share of a K / V^T tile's DMA
+    constexpr int QPW = Q_BYTES / 1024 / NW;       // 1-KiB DMA pieces per wave of the Q tile
+    constexpr int PIECES = TPS * (Stream::KPW + Stream::VPW);      // per wave per stage
     constexpr int K_CPR = D / 8;                   // 16-B chunks per K (and Q) row
-    static_assert(KPW >= 1 && VPW >= 1 && QPW >= 1, "every wave moves at least one piece of every tile");
+    static_assert(QPW >= 1, "every wave moves at least one piece of the Q tile");
 
     // LDS: [ring of NSTG stages of TPS x (K tile | V^T tile)] [Q tile]; the ring is reused for the merge + store staging
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -582,45 +531,16 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
     // ---- LDS-DMA (no VGPR staging): the split's first NSTG stages are requested before the row bookkeeping; a tile that lies
     // beyond the split is a harmless read inside the cache allocation (an L2 hit of the split's first tile) and is never computed on
     const int last_tile = a.S_max / KT - 1;
-    // per-lane byte offsets of this wave's pieces inside a K tile / a V^T tile, resolved ONCE: a piece of a tile is then (wave-uniform tile
-    // base) + (32-bit lane offset) - one scalar add per piece instead of a 64-bit multiply-add per lane.  (The prologue's 16 pieces per wave
-    // took 4 k cycles to issue; every cycle of it delays the moment the split's stream is fully requested.)
-    uint32_t k_off[KPW], v_off[VPW];
-#pragma unroll
-    for (int i = 0; i < KPW; ++i) {
-        const int piece = wave * KPW + i;
-        const int row = piece * (64 / K_CPR) + lane / K_CPR;
-        const int c = (lane % K_CPR) ^ swz16<2 * D>(row);
-        k_off[i] = (uint32_t)(row * D + c * 8) * 2u;
-    }
-#pragma unroll
-    for (int i = 0; i < VPW; ++i) {
-        const int piece = wave * VPW + i;
-        const int row = piece * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ swz16<2 * KT>(row);
-        v_off[i] = ((uint32_t)row * (uint32_t)a.S_max + (uint32_t)(c * 8)) * 2u;
-    }
+    // (the per-lane piece offsets are resolved once: the prologue's 16 pieces per wave took 4 k cycles to issue, and every cycle of it
+    // delays the moment the split's stream is fully requested)
+    const Stream kv(wave, lane, a.S_max);
     const unsigned char* kbytes = reinterpret_cast<const unsigned char*>(kbase);
     const unsigned char* vbytes = reinterpret_cast<const unsigned char*>(vbase);
     auto issue_tiles_aux = [&](int stage, int ts, int tile, auto aux_c) {
         constexpr int AUX = decltype(aux_c)::value;          // cache-policy bits of the K / V loads: 1 = sc0, 2 = nt, 16 = sc1
         const int k0 = min(tile, last_tile) * KT;
         unsigned char* ks = smem + stage * STAGE_BYTES + ts * TILE_BYTES;
-        unsigned char* vs = ks + K_BYTES;
-        const unsigned char* kt = kbytes + (size_t)k0 * D * 2;          // wave uniform
-        const unsigned char* vt = vbytes + (size_t)k0 * 2;
-#pragma unroll
-        for (int i = 0; i < KPW; ++i) {
-            const int piece = wave * KPW + i;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kt + k_off[i]),
-                                             (__attribute__((address_space(3))) void*)(ks + piece * 1024), 16, 0, AUX);
-        }
-#pragma unroll
-        for (int i = 0; i < VPW; ++i) {
-            const int piece = wave * VPW + i;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vt + v_off[i]),
-                                             (__attribute__((address_space(3))) void*)(vs + piece * 1024), 16, 0, AUX);
-        }
+        kv.template issue<AUX>(kbytes + (size_t)k0 * D * 2, vbytes + (size_t)k0 * 2, ks, ks + K_BYTES);
     };
     int sc1_from_q = 1 << 30;            // producer mode: tiles (offsets within the split) from this one on hold rows a producer wrote in THIS launch: sc1 loads
     // cache policy of the K / V stream: a COMPILE-time constant (LADE_KV_AUX; bits 1 = sc0, 2 = nt, 16 = sc1) - variants are separate builds
@@ -841,13 +761,8 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
         for (int ts = 0; ts < TPS; ++ts) {
             const int kt0 = tile_of(i, ts) * KT;
             if (i * TPS + ts < my_tiles && kt0 + KT > S_tot) {          // work-group uniform
-                // last tile: V^T columns of keys >= P+T hold stale bytes; zero them (0 * NaN would poison O)
-                unsigned char* vw = smem + stage * STAGE_BYTES + ts * TILE_BYTES + K_BYTES;
-                const int first = S_tot - kt0;
-                for (int idx = tid; idx < D * (KT - first); idx += NTHR) {
-                    const int row = idx / (KT - first), key = first + idx % (KT - first);
-                    *reinterpret_cast<uint16_t*>(vw + tile_off<2 * KT>(row, key >> 3) + (key & 7) * 2) = 0;
-                }
+                // last tile: the V^T columns of keys >= P+T hold stale bytes
+                zero_stale_vt<D>(smem + stage * STAGE_BYTES + ts * TILE_BYTES + K_BYTES, S_tot - kt0, tid, NTHR);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 wg_barrier();
             }
@@ -875,52 +790,18 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
 #pragma unroll
             for (int db = 0; db < DBLK; ++db) vf0[db] = *reinterpret_cast<const u32x4*>(vs + tile_off<2 * KT>(db * 32 + ql, 4 * kh + 2 * hi));
             // ---- online softmax in the log2 domain; lane (q, hi) holds keys 32kh + 16hi + e ----
-            float tmax = NEG_BIG;
-            if (full) {
+            scale_scores(sacc, a.scale_log2);
+            if (!full) {
 #pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    sacc[e] *= a.scale_log2;
-                    tmax = fmaxf(tmax, sacc[e]);
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float sv = ((bits >> e) & 1u) ? sacc[e] * a.scale_log2 : MASKED;
-                    sacc[e] = sv;
-                    tmax = fmaxf(tmax, sv);
-                }
+                for (int e = 0; e < 16; ++e) sacc[e] = ((bits >> e) & 1u) ? sacc[e] : MASKED;
             }
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-            // raise the running max only when it grows by more than RESCALE_THR (wave-uniform decision):
-            // p stays <= 2^THR, harmless in the fp32 accumulators, and the O^T rescale is skipped on most tiles
-            if (__builtin_amdgcn_ballot_w64(tmax > m_run + RESCALE_THR) != 0ull) {
-                const float m_new = fmaxf(m_run, tmax);
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-                m_run = m_new;
-                l_run *= alpha;
-#pragma unroll
-                for (int ii = 0; ii < DBLK; ++ii)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) oacc[ii][e] *= alpha;
-            }
-            float psum = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float p = __builtin_amdgcn_exp2f(sacc[e] - m_run);   // masked: 2^(-3e30 - m) = 0
-                sacc[e] = p;
-                psum += p;
-            }
-            l_run += psum;
+            softmax_update(sacc, m_run, l_run, oacc);
             // ---- O^T += V^T P^T : k-step jj = keys 32kh + 16hi + 8jj + 0..7 ----
             u32x4 vf1[DBLK];
 #pragma unroll
             for (int db = 0; db < DBLK; ++db) vf1[db] = *reinterpret_cast<const u32x4*>(vs + tile_off<2 * KT>(db * 32 + ql, 4 * kh + 2 * hi + 1));
             u32x4 pf0, pf1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pf0[e] = pack2<T>(sacc[2 * e], sacc[2 * e + 1]);
-                pf1[e] = pack2<T>(sacc[8 + 2 * e], sacc[8 + 2 * e + 1]);
-            }
+            pack_p<T>(sacc, pf0, pf1);
 #pragma unroll
             for (int db = 0; db < DBLK; ++db) oacc[db] = Mfma<T>::run(vf0[db], pf0, oacc[db]);
 #pragma unroll
@@ -980,13 +861,9 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
             // the same expression in both waves, always in key-part order (part 0, part 1): identical m and l on both sides
             const float m0 = P0 ? m_run : mlo.x, m1 = P0 ? mlo.x : m_run;
             const float l0 = P0 ? l_run : mlo.y, l1 = P0 ? mlo.y : l_run;
-            const float mm = fmaxf(m0, m1);
-            const float a0 = __builtin_amdgcn_exp2f(m0 - mm), a1 = __builtin_amdgcn_exp2f(m1 - mm);
-            float lsum = __builtin_fmaf(l0, a0, l1 * a1);
+            const PairMerge pm = pair_merge(m0, l0, m1, l1);
             dbg_stamp(a, 4);
-            lsum += __shfl_xor(lsum, 32);
-            const float inv = lsum > 0.f ? __builtin_amdgcn_rcpf(lsum) : 0.f;      // 1 ulp; the result is rounded to 16 bits
-            const float s_own = (P0 ? a0 : a1) * inv, s_oth = (P0 ? a1 : a0) * inv;
+            const float s_own = P0 ? pm.s0 : pm.s1, s_oth = P0 ? pm.s1 : pm.s0;
             unsigned char* stg = stg_base + (size_t)rg * stg_stride;
 #pragma unroll
             for (int h = 0; h < HALF; ++h)
@@ -994,13 +871,13 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const float4 o1 = in[h * 4 + g4];
                     u32x2 w;
-                    w[0] = pack2<T>(__builtin_fmaf(oacc[KEEP + h][4 * g4 + 0], s_own, o1.x * s_oth), __builtin_fmaf(oacc[KEEP + h][4 * g4 + 1], s_own, o1.y * s_oth));
-                    w[1] = pack2<T>(__builtin_fmaf(oacc[KEEP + h][4 * g4 + 2], s_own, o1.z * s_oth), __builtin_fmaf(oacc[KEEP + h][4 * g4 + 3], s_own, o1.w * s_oth));
+                    w[0] = pack2<T>(merged_elem(oacc[KEEP + h][4 * g4 + 0], s_own, o1.x, s_oth), merged_elem(oacc[KEEP + h][4 * g4 + 1], s_own, o1.y, s_oth));
+                    w[1] = pack2<T>(merged_elem(oacc[KEEP + h][4 * g4 + 2], s_own, o1.z, s_oth), merged_elem(oacc[KEEP + h][4 * g4 + 3], s_own, o1.w, s_oth));
                     *reinterpret_cast<u32x2*>(stg + ql * RS + ((KEEP + h) * 32 + 8 * g4 + 4 * hi) * 2) = w;
                 }
             if (P0 && a.n_splits > 1 && valid && hi == 0) {
                 const size_t prow = ((size_t)sp * a.H + qh) * m.T + t;
-                *reinterpret_cast<float2*>(a.part_ml + prow * 2) = float2{mm, lsum};
+                *reinterpret_cast<float2*>(a.part_ml + prow * 2) = float2{pm.mm, pm.lsum};
             }
         };
         if (kq == 0) swap_merge(std::true_type{});

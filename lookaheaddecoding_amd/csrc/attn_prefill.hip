@@ -6,7 +6,8 @@
 // arithmetic intensity far above the ridge, MFMA / VALU bound.  So the decomposition changes while the formulation stays:
 //
 //   * the transposed formulation of attn.hip: S^T = K Q^T, O^T = V^T P^T on v_mfma_f32_32x32x16, one query row per lane (the row statistics
-//     are lane-local), kappa() key order, XOR-swizzled ds_read_b128 fragments, LDS-DMA ring;
+//     are lane-local), kappa() key order, XOR-swizzled ds_read_b128 fragments, LDS-DMA ring - the shared formulation, and every piece of
+//     arithmetic that decides an output bit, is attn_core.hpp's, which both kernels call;
 //   * a work-group of 8 waves owns 256 rows of the (head-in-group, token) row space; wave w owns rows 32w .. 32w+31 and ALL 64 keys of every
 //     tile: a K / V^T tile is filled and read once per 256 rows, and there is no key-part exchange at the end;
 //   * no KV split and no partial buffers: row block rb of KV head kvh walks the tiles 0 .. (P + its last token) / 64 and writes `out`;
@@ -22,25 +23,15 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "attn_core.hpp"
 
 namespace lade {
 namespace pf {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int KT = 64;                  // keys per tile
 constexpr int NW = 8;                   // waves per work-group
 constexpr int NTHR = 64 * NW;
 constexpr int ROWS = 32 * NW;           // query rows per work-group
 constexpr int NSTG = 3;                 // ring depth
-constexpr float NEG_BIG = -1.0e30f;     // initial running max
-constexpr float MASKED = -3.0e30f;      // masked (scaled) score: 2^(MASKED - m) == 0 even while m is still NEG_BIG
-constexpr float RESCALE_THR = 8.0f;     // log2 units: the running max is only raised when it grows by more (attn.hip)
 // cache policy of the K / V stream (bits 1 = sc0, 2 = nt, 16 = sc1): the DEFAULT policy here, unlike the decode kernel's non-temporal stream -
 // the row blocks of a KV head re-read the same tiles, and the L2 of their XCD is where they should find them
 constexpr int KV_AUX = 0;
@@ -55,45 +46,13 @@ struct PrefillK {
     float scale_log2;                   // scale * log2(e)
 };
 
-// 16-B chunk swizzle of a row-major tile (attn.hip: applied to the DMA's per-lane SOURCE address and to the read address)
-template <int ROW_BYTES>
-__device__ __forceinline__ int swz16(int row) {
-    constexpr int CPR = ROW_BYTES / 16;
-    constexpr int RPB = 256 / ROW_BYTES > 0 ? 256 / ROW_BYTES : 1;
-    return (row / RPB) & (CPR - 1);
-}
-template <int ROW_BYTES>
-__device__ __forceinline__ int tile_off(int row, int c16) { return row * ROW_BYTES + ((c16 ^ swz16<ROW_BYTES>(row)) << 4); }
-
-// MFMA row index rho (0..31) of an S^T sub-tile <-> key within the sub-tile: a lane's 16 S^T values are 16 CONTIGUOUS keys (attn.hip)
-__device__ __forceinline__ int kappa(int rho) { return (rho & 3) | (((rho >> 3) & 3) << 2) | (((rho >> 2) & 1) << 4); }
-
-template <typename T> struct Mfma;
-template <> struct Mfma<BF16> {
-    __device__ static __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mfma<F16> {
-    __device__ static __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-
-// work-group barrier that the compiler cannot move memory operations across (attn.hip)
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_barrier" ::: "memory"); }
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 template <typename T, int D>
 __global__ __launch_bounds__(NTHR) void attn_prefill_kernel(PrefillK a) {
     constexpr int KSTEPS = D / 16;                 // MFMA k-steps of S^T
     constexpr int DBLK = D / 32;                   // 32-row blocks of O^T
     constexpr int K_BYTES = KT * D * 2, V_BYTES = D * KT * 2, STAGE_BYTES = K_BYTES + V_BYTES;
-    constexpr int KPW = K_BYTES / 1024 / NW;       // 1-KiB DMA pieces per wave per tile
-    constexpr int VPW = V_BYTES / 1024 / NW;
-    constexpr int PIECES = KPW + VPW;
-    constexpr int K_CPR = D / 8;                   // 16-B chunks per K row
-    static_assert(KPW >= 1 && VPW >= 1, "every wave moves at least one piece of every tile");
+    using Stream = KvStream<D, NW>;                // this wave's share of a tile's DMA
+    constexpr int PIECES = Stream::KPW + Stream::VPW;      // per wave per tile
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // ring of NSTG x (K tile | V^T tile); reused for the store staging
 
@@ -146,37 +105,13 @@ __global__ __launch_bounds__(NTHR) void attn_prefill_kernel(PrefillK a) {
         if (w0 + 31 >= n_rows) w_full = min(w_full, (P / KT) * 2);      // a wave with padding lanes: they see the cache's whole tiles only
     }
 
-    // ---- LDS-DMA: per-lane byte offsets of this wave's pieces inside a K tile / a V^T tile, resolved once
+    // ---- LDS-DMA stream of this KV head's K / V^T tiles
     const unsigned char* kbytes = reinterpret_cast<const unsigned char*>(a.k + (size_t)kvh * a.S_max * D);
     const unsigned char* vbytes = reinterpret_cast<const unsigned char*>(a.vt + (size_t)kvh * D * a.S_max);
-    uint32_t k_off[KPW], v_off[VPW];
-#pragma unroll
-    for (int i = 0; i < KPW; ++i) {
-        const int piece = wave * KPW + i;
-        const int row = piece * (64 / K_CPR) + lane / K_CPR;
-        const int c = (lane % K_CPR) ^ swz16<2 * D>(row);
-        k_off[i] = (uint32_t)(row * D + c * 8) * 2u;
-    }
-#pragma unroll
-    for (int i = 0; i < VPW; ++i) {
-        const int piece = wave * VPW + i;
-        const int row = piece * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ swz16<2 * KT>(row);
-        v_off[i] = ((uint32_t)row * (uint32_t)a.S_max + (uint32_t)(c * 8)) * 2u;      // < 2^32: S_max <= 2^22 (checked on the host)
-    }
+    const Stream kv(wave, lane, a.S_max);
     auto issue_tile = [&](int tile, int stage) {
         unsigned char* ks = smem + stage * STAGE_BYTES;
-        unsigned char* vs = ks + K_BYTES;
-        const unsigned char* kt = kbytes + (size_t)tile * KT * D * 2;       // wave uniform
-        const unsigned char* vt = vbytes + (size_t)tile * KT * 2;
-#pragma unroll
-        for (int i = 0; i < KPW; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kt + k_off[i]),
-                                             (__attribute__((address_space(3))) void*)(ks + (wave * KPW + i) * 1024), 16, 0, KV_AUX);
-#pragma unroll
-        for (int i = 0; i < VPW; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vt + v_off[i]),
-                                             (__attribute__((address_space(3))) void*)(vs + (wave * VPW + i) * 1024), 16, 0, KV_AUX);
+        kv.template issue<KV_AUX>(kbytes + (size_t)tile * KT * D * 2, vbytes + (size_t)tile * KT * 2, ks, ks + K_BYTES);
     };
     issue_tile(0, 0);
     issue_tile(min(1, a.S_max / KT - 1), 1);       // unconditional (a one-tile block re-reads tile 0 or reads a tile it never computes): the wait below stays counted
@@ -185,10 +120,10 @@ __global__ __launch_bounds__(NTHR) void attn_prefill_kernel(PrefillK a) {
 #pragma unroll
     for (int kk = 0; kk < KSTEPS; ++kk) asm volatile("" : "+v"(qf[kk]));
 
-    // Two online-softmax states per row, one per 32-key half kh of every tile, merged at the end: the arithmetic of attn_fwd_kernel's 128-row
-    // shape (there the two halves live in two waves), operation for operation - lade_attn_prefill returns the bits lade_attn_fwd returns
-    // with n_splits = 1 (tests/test_gpu_attn_prefill.py), so routing a chunk to this kernel changes no token.  The two states are also two
-    // independent dependency chains for the scheduler.
+    // Two online-softmax states per row, one per 32-key half kh of every tile, merged at the end: the state of attn_fwd_kernel's 128-row
+    // shape (there the two halves live in two waves), moved on by the same attn_core.hpp calls - lade_attn_prefill returns the bits
+    // lade_attn_fwd returns with n_splits = 1 (tests/test_gpu_attn_prefill.py), so routing a chunk to this kernel changes no token.  The two
+    // states are also two independent dependency chains for the scheduler.
     f32x16 oacc[2][DBLK];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -225,46 +160,20 @@ __global__ __launch_bounds__(NTHR) void attn_prefill_kernel(PrefillK a) {
         u32x4 vf0[DBLK];
 #pragma unroll
         for (int db = 0; db < DBLK; ++db) vf0[db] = *reinterpret_cast<const u32x4*>(smem + (vb ^ ((4 * kh) << 4)) + db * 32 * 2 * KT);
-        // lane (q, hi) holds the scores of keys k0 + 32 kh + 16 hi + e.  Separately rounded multiply and subtract (no fma): attn_fwd_kernel's bits
-#pragma unroll
-        for (int e = 0; e < 16; ++e) s[e] = __fmul_rn(s[e], sc);
+        // lane (q, hi) holds the scores of keys k0 + 32 kh + 16 hi + e
+        scale_scores(s, sc);
         if (masked) {
             const int lim = kmax - k0 - 32 * kh - 16 * hi;           // key offset e is visible iff <= lim
 #pragma unroll
             for (int e = 0; e < 16; ++e) s[e] = (e <= lim) ? s[e] : MASKED;      // a select: NaN of rows that do not exist never gets further
         }
-        float tmax = NEG_BIG;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) tmax = fmaxf(tmax, s[e]);
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-        if (__builtin_amdgcn_ballot_w64(tmax > m_run[kh] + RESCALE_THR) != 0ull) {       // wave uniform: the O^T rescale is skipped on most tiles
-            const float m_new = fmaxf(m_run[kh], tmax);
-            const float alpha = __builtin_amdgcn_exp2f(m_run[kh] - m_new);
-            m_run[kh] = m_new;
-            l_run[kh] *= alpha;
-#pragma unroll
-            for (int ii = 0; ii < DBLK; ++ii)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) oacc[kh][ii][e] *= alpha;
-        }
-        float psum = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float p = __builtin_amdgcn_exp2f(__fsub_rn(s[e], m_run[kh]));   // masked: 2^(-3e30 - m) = 0
-            s[e] = p;
-            psum += p;
-        }
-        l_run[kh] += psum;
+        softmax_update(s, m_run[kh], l_run[kh], oacc[kh]);
         // k-step jj = keys 32 kh + 16 hi + 8 jj + 0..7 = 16-byte chunk 4 kh + 2 hi + jj of a V^T row
         u32x4 vf1[DBLK];
 #pragma unroll
         for (int db = 0; db < DBLK; ++db) vf1[db] = *reinterpret_cast<const u32x4*>(smem + (vb ^ ((4 * kh + 1) << 4)) + db * 32 * 2 * KT);
         u32x4 pf0, pf1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            pf0[e] = pack2<T>(s[2 * e], s[2 * e + 1]);
-            pf1[e] = pack2<T>(s[8 + 2 * e], s[8 + 2 * e + 1]);
-        }
+        pack_p<T>(s, pf0, pf1);
 #pragma unroll
         for (int db = 0; db < DBLK; ++db) oacc[kh][db] = Mfma<T>::run(vf0[db], pf0, oacc[kh][db]);
 #pragma unroll
@@ -283,13 +192,7 @@ __global__ __launch_bounds__(NTHR) void attn_prefill_kernel(PrefillK a) {
         if (i + 2 < n_tiles) issue_tile(i + 2, (i + 2) % NSTG);
         const int k0 = i * KT;
         if (k0 + KT > S_tot) {          // work-group uniform, the chunk's last tile only
-            // V^T columns of keys >= P + T hold whatever the cache held; zero them (0 * NaN would poison O)
-            const int first = S_tot - k0;
-#pragma clang loop vectorize(disable) unroll(disable)
-            for (int idx = tid; idx < D * KT; idx += NTHR) {
-                const int row = idx >> 6, key = idx & 63;
-                if (key >= first) *reinterpret_cast<uint16_t*>(vs + tile_off<2 * KT>(row, key >> 3) + (key & 7) * 2) = 0;
-            }
+            zero_stale_vt<D>(vs, S_tot - k0, tid, NTHR);      // the V^T columns of keys >= P + T hold whatever the cache held
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             wg_barrier();
         }
@@ -307,17 +210,11 @@ __global__ __launch_bounds__(NTHR) void attn_prefill_kernel(PrefillK a) {
     constexpr int RS = 2 * D + 16;      // staging row stride (bytes), 16-B aligned
     static_assert((size_t)ROWS * RS <= (size_t)NSTG * STAGE_BYTES, "staging rows fit in the ring");
     unsigned char* stg = smem + (size_t)wave * 32 * RS;
-    // merge of the two key halves, as attn_fwd_kernel's two waves of a row group do it: the wave of half 0 finishes the lower d-blocks
-    // (own = half 0), the wave of half 1 the upper ones (own = half 1) - out = fma(o_own, s_own, o_other * s_other)
-    const float mm = fmaxf(m_run[0], m_run[1]);
-    const float a0 = __builtin_amdgcn_exp2f(m_run[0] - mm), a1 = __builtin_amdgcn_exp2f(m_run[1] - mm);
-    float lsum = __builtin_fmaf(l_run[0], a0, __fmul_rn(l_run[1], a1));
-    lsum += __shfl_xor(lsum, 32);
-    const float inv = lsum > 0.f ? __builtin_amdgcn_rcpf(lsum) : 0.f;      // 1 ulp; the result is rounded to 16 bits
-    const float s0 = __fmul_rn(a0, inv), s1 = __fmul_rn(a1, inv);
+    // merge of the two key halves, with attn_fwd_kernel's ownership convention: there the wave of half 0 finishes the lower d-blocks
+    // (own = half 0) and the wave of half 1 the upper ones (own = half 1)
+    const PairMerge pm = pair_merge(m_run[0], l_run[0], m_run[1], l_run[1]);
     auto merged = [&](int db, int e) {
-        return db < DBLK / 2 ? __builtin_fmaf(oacc[0][db][e], s0, __fmul_rn(oacc[1][db][e], s1))
-                             : __builtin_fmaf(oacc[1][db][e], s1, __fmul_rn(oacc[0][db][e], s0));
+        return db < DBLK / 2 ? merged_elem(oacc[0][db][e], pm.s0, oacc[1][db][e], pm.s1) : merged_elem(oacc[1][db][e], pm.s1, oacc[0][db][e], pm.s0);
     };
 #pragma unroll
     for (int db = 0; db < DBLK; ++db)

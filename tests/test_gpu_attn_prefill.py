@@ -52,13 +52,14 @@ def test_case_table_covers_every_head_set_in_both_dtypes():
     assert any(c[2] == (8, 1, 64) and c[0] % 32 for c in cs)          # n_rep = 8 at d = 64 with a chunk that is no multiple of 32
 
 
-def _inputs(T, P, H, Hkv, d, dtype, seed, S_max=None, strided=False, fill=0.0):
+def _inputs(T, P, H, Hkv, d, dtype, seed, S_max=None, strided=False, fill=0.0, k_growth=0.0):
+    """k_growth: the K rows of 64-key tile i are scaled by 1 + k_growth * i (scores that keep growing along the cache)"""
     g = torch.Generator().manual_seed(seed)
     S = P + T
     S_max = S_max or (S + 63) // 64 * 64
     k = torch.full((Hkv, S_max, d), fill).to(dtype)
     v = torch.full((Hkv, S_max, d), fill).to(dtype)
-    k[:, :S] = torch.randn(Hkv, S, d, generator=g).to(dtype)
+    k[:, :S] = (torch.randn(Hkv, S, d, generator=g) * (1.0 + k_growth * (torch.arange(S) // 64)).view(1, S, 1)).to(dtype)
     v[:, :S] = torch.randn(Hkv, S, d, generator=g).to(dtype)
     q = torch.randn(T, H * d, generator=g).to(dtype)
     if strided:                                      # q stays inside a qkv buffer: row stride (H + 2 Hkv) d
@@ -119,15 +120,65 @@ BITWISE = [(2065, 0, (32, 32, 128), torch.bfloat16), (2065, 100, (4, 4, 128), to
            (777, 70, (8, 2, 128), torch.float16), (2303, 31, (4, 1, 64), torch.bfloat16)]
 
 
-@pytest.mark.parametrize("T,P,heads,dtype", BITWISE, ids=lambda x: str(x).replace("torch.", "").replace(" ", ""))
-def test_prefill_attention_equals_the_single_launch_decode_kernel_bit_for_bit(T, P, heads, dtype):
+# Small shapes on the same equality: a break in the arithmetic the two kernels share (csrc/attn_core.hpp) shows up in a test of a second.  The
+# kernel entry point takes any T > 0 (the "more than 256 rows" rule is tuning.use_prefill_attn's, not the kernel's).
+#   T=33 P=31 (2,2,64): one full wave plus a one-row wave, P inside the first 32-key sub-tile, a single tile;
+#   T=70 P=90 (4,1,128): n_rep = 4 stacks 280 rows - two row blocks, waves that straddle heads, P + T = 160 leaves the last tile half stale;
+#   T=96 P=0 (1,1,128): the diagonal alone, masked / unmasked sub-tile boundaries on multiples of 32;
+#   T=40 P=1000 (8,8,64): unmasked cache tiles first, then the band;
+#   T=64 P=448 (2,2,128) with K rows growing along the cache: the lazy rescale fires again and again (checked on the CPU before the launch).
+RESCALE_GROWTH = 3.0
+BITWISE_SMALL = [(33, 31, (2, 2, 64), torch.bfloat16, 0.0), (33, 31, (2, 2, 64), torch.float16, 0.0), (70, 90, (4, 1, 128), torch.bfloat16, 0.0),
+                 (70, 90, (4, 1, 128), torch.float16, 0.0), (96, 0, (1, 1, 128), torch.bfloat16, 0.0), (40, 1000, (8, 8, 64), torch.float16, 0.0),
+                 (64, 448, (2, 2, 128), torch.bfloat16, RESCALE_GROWTH)]
+RESCALE_THR = 8.0               # csrc/attn_core.hpp: the running max (log2 units) is only raised when it grows by more
+
+
+def _bitwise_id(case):
+    return "-".join(str(x).replace("torch.", "").replace(" ", "") for x in (case if case[4] else case[:4]))
+
+
+def _rescale_rises(q, k, T, P, H, Hkv, d):
+    """Per (query row, 32-key half of a tile) state: how often the row's running max rises by more than RESCALE_THR after its first tile, under
+    the kernels' rule - the 32 rows of a wave decide together (a rescale when ANY of them sees its sub-tile maximum exceed its running max by
+    more than the threshold; then every row takes max(m, sub-tile max)).  Scores from the rounded inputs: q . k * scale * log2(e), causal."""
+    n_rep, S = H // Hkv, P + T
+    s = torch.einsum("thd,hkd->htk", q.float().view(T, H, d), k.float()[:, :S].repeat_interleave(n_rep, 0)) * (1.4426950408889634 / math.sqrt(d))
+    s = s.masked_fill(~torch.as_tensor(_causal(T, P)), float("-inf"))
+    n_tiles = (S + 63) // 64
+    s = torch.nn.functional.pad(s, (0, n_tiles * 64 - S), value=float("-inf"))
+    tmax = s.view(Hkv, n_rep * T, n_tiles, 2, 32).amax(-1)                  # [KV head][row of the (head-in-group, token) space][tile][half]
+    rises = torch.zeros(Hkv, n_rep * T, 2, dtype=torch.int64)
+    for r0 in range(0, n_rep * T, 32):                                      # a wave's rows (row blocks are multiples of 32 rows in both kernels)
+        m = torch.full((Hkv, min(32, n_rep * T - r0), 2), -1.0e30)
+        for i in range(n_tiles):
+            t = tmax[:, r0:r0 + 32, i]
+            own = t > m + RESCALE_THR
+            fire = own.any(1, keepdim=True)
+            rises[:, r0:r0 + 32] += (own & fire & (m > -1.0e29)).long()
+            m = torch.where(fire, torch.maximum(m, t), m)
+    return rises
+
+
+BITWISE_CASES = [c + (0.0,) for c in BITWISE] + BITWISE_SMALL
+
+
+@pytest.mark.parametrize("T,P,heads,dtype,k_growth", BITWISE_CASES, ids=[_bitwise_id(c) for c in BITWISE_CASES])
+def test_prefill_attention_equals_the_single_launch_decode_kernel_bit_for_bit(T, P, heads, dtype, k_growth):
     """lade_attn_prefill keeps one online-softmax state per 32-key half of a tile and merges them as lade_attn_fwd's two waves of a row group
     do: its output is lade_attn_fwd's with n_splits = 1 (what the engine launched for a chunk that fills the chip by itself - bench.py's
     2065-row pass among them), bit for bit, so routing such a chunk to it changes no logit and no token.  Chunks with a partial last wave
-    (T not a multiple of 32), heads stacked in the row space, P inside a tile and P = 0 are all in."""
+    (T not a multiple of 32), heads stacked in the row space, P inside a tile and P = 0 are all in; so are small shapes (BITWISE_SMALL), one of
+    them with K rows that grow along the cache so that the lazy rescale of a state fires at least twice more after its first tile."""
     from lookaheaddecoding_amd import ops
     H, Hkv, d = heads
-    _, _, _, qd, kd, vtd = _inputs(T, P, H, Hkv, d, dtype, seed=T + P, S_max=(P + T + 63) // 64 * 64 + 128, strided=True, fill=float("nan"))
+    q, k, _, qd, kd, vtd = _inputs(T, P, H, Hkv, d, dtype, seed=T + P, S_max=(P + T + 63) // 64 * 64 + 128, strided=True, fill=float("nan"), k_growth=k_growth)
+    if k_growth:
+        rises = _rescale_rises(q, k, T, P, H, Hkv, d)
+        frac = (rises >= 2).float().mean().item()
+        print(f"T={T} P={P} heads={heads} growth {k_growth}: {frac:.1%} of the (row, half) states rise by more than {RESCALE_THR} at least twice; "
+              f"mean {rises.float().mean().item():.2f} rises")
+        assert frac > 0.75, (frac, rises.float().mean().item())
     m = ops.StepMask(T=T, P=P, is_prefill=True)
     new = ops.attn_prefill(qd, kd, vtd, m, H=H, Hkv=Hkv, d=d)
     old = ops.attn_fwd(qd, kd, vtd, m, H=H, Hkv=Hkv, d=d, n_splits=1)
