@@ -64,9 +64,11 @@
 extern "C" {
 #endif
 
-#define LADE_ABI_VERSION 3      /* 2: lade_attn_args grew (wg_rows, fused RoPE), lade_gemm_skinny* take `ring`, lade_greedy_post_step takes record_host;
+#define LADE_ABI_VERSION 4      /* 2: lade_attn_args grew (wg_rows, fused RoPE), lade_gemm_skinny* take `ring`, lade_greedy_post_step takes record_host;
                                  * 3: + lade_gemm_ra_kt, lade_build_flags; + lade_gen_ctl_init, lade_gen_ctl_update, lade_gen_argmax,
-                                 *    lade_gen_rows, lade_greedy_post_step_ex (nothing that existed changed) */
+                                 *    lade_gen_rows, lade_greedy_post_step_ex (nothing that existed changed);
+                                 * 4: the measured-and-dropped kernels are gone: lade_attn_args ends at wg_rows (n_parts, qkv_parts, part_stride, positions,
+                                 *    cos_tab, sin_tab, max_pos, sync_flags removed), lade_gemm_ra_kt and lade_build_flags removed; nothing else changed */
 
 /* error codes */
 #define LADE_OK 0
@@ -151,23 +153,6 @@ typedef struct lade_attn_args {
     int32_t wg_rows;        /* work-group shape: query rows of the (head-in-group, token) row space per work-group - 128 (4 x 2 waves, one 64-key
                              * tile per stage), 64 or 32 (two tiles per stage, every wave computes); 0 = 128.  A launch parameter like the GEMM's
                              * tile shape: the caller's in-step autotune picks it per launch shape together with n_splits */
-    /* Fused RoPE + KV append (n_parts > 0; bf16 / f16): q and the step's new K / V rows are taken from the qkv projection's fp32 split-K
-     * partials instead of from `q` and the cache - the work of lade_rope_kv_append_parts (lade/models/modeling_llama.py:321-346, :510-516)
-     * inside this launch, operation for operation: the rows P .. P+T of k_cache / vt_cache are WRITTEN (by the work-groups whose key range
-     * holds them) and the results are bit-identical to the two-launch form.  `q` may be null. */
-    int32_t n_parts;        /* 0 = off; 1..4 partials */
-    const float* qkv_parts; /* [n_parts][T][(H + 2 Hkv) d], part_stride elements apart */
-    int64_t part_stride;
-    const int32_t* positions;   /* [T] position ids (rows of the tables), or null: token t uses table row t (per-step gathered rows) */
-    const void* cos_tab;    /* [max_pos][d], model dtype; the fused form needs tables whose two halves are equal (emb = cat(freqs, freqs)) */
-    const void* sin_tab;
-    int32_t max_pos;
-    /* Producer mode of the fused form (non-null; needs n_splits > 1 and `q`): instead of every KV split rebuilding its head's q rows, the
-     * first work-groups of the grid do the RoPE + append work ONCE per (KV head, 32 tokens) - rotated q rows to `q`, K / V rows to the
-     * caches, write-through - and raise sync_flags[kvh]; the attention work-groups of that head request the cache tiles that hold no new
-     * row, poll the flag from one lane (bounded: a launch never hangs) and then fetch q and the other tiles.  sync_flags: device
-     * int32[Hkv], zero before the first launch; lade_attn_combine (which must follow) zeroes it again. */
-    int32_t* sync_flags;
 } lade_attn_args;
 
 int lade_attn_fwd(const lade_attn_args* a, void* stream);
@@ -179,7 +164,7 @@ int lade_attn_combine(const lade_attn_args* a, void* stream);
  * work-groups of 8 waves x 32 query rows, every K / V^T tile staged once per 256 rows, tiles above a block's diagonal never requested,
  * longest blocks first, ONE launch and no partial buffers.
  * The engine launches it only under LADE_DEBUG=prefill_attn=1.
- * Takes lade_attn_args as it is and requires: mask.is_prefill == 1 (row t of the chunk sees keys 0 .. P + t), n_parts == 0, sync_flags == NULL,
+ * Takes lade_attn_args as it is and requires: mask.is_prefill == 1 (row t of the chunk sees keys 0 .. P + t),
  * dyn_P == NULL, dtype LADE_BF16 or LADE_F16, d = 64 or 128, S_max a multiple of 64 (at most 2^22) and >= P + T, q / out 16-byte aligned with
  * row strides that are multiples of 8 elements (q may be a view into the qkv buffer).  Anything else returns LADE_E_ARG with a message.
  * Reads k_cache [Hkv][S_max][d] and vt_cache [Hkv][d][S_max] (rows P .. P+T already appended), writes out [T][H][d].  n_splits, wg_rows,
@@ -477,14 +462,6 @@ int lade_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t ldw, voi
 int lade_gemm_skinny_kt(const void* A, int64_t lda, const void* Wkt, void* C, int64_t ldc, float* Cpart,
                         int32_t M, int32_t N, int32_t K, int32_t n_split, int32_t bn, int32_t mb, int32_t mt, int32_t nt,
                         int32_t ring, int32_t epilogue, int32_t dtype, void* stream);
-/* Split-K GEMM with REGISTER-RESIDENT activations for steps of M <= 128 rows (the same projections, lade/models/modeling_llama.py:360-380,
- * 492-494, 558): a work-group is persistent over the weight rows of its column group and keeps the activation fragments of its K slice
- * (<= 20 K tiles = 1280 deep: ceil(K / 64 / n_split) <= 20) in registers, so the activations pass through a CU once per work-group and the
- * whole LDS is a ring of weight tiles.  Writes fp32 partials Cpart[n_split][M][N] for a `*_parts` consumer - bit-identical to
- * lade_gemm_skinny_kt's with the same n_split.  cs = 32-row weight strips per chunk (2 | 4; N % (32 cs) == 0), n_groups = column groups
- * per split (0 = CUs / n_split; the launch has n_groups * n_split work-groups, one per CU). */
-int lade_gemm_ra_kt(const void* A, int64_t lda, const void* Wkt, float* Cpart, int32_t M, int32_t N, int32_t K, int32_t n_split,
-                    int32_t cs, int32_t n_groups, int32_t dtype, void* stream);
 int lade_weight_to_ktile(const void* W, int64_t ldw, void* Wkt, int32_t N, int32_t K, int32_t dtype, void* stream);
 /* the inverse, into a caller-provided row-major scratch W[N][ldw]: what a library GEMM needs (prefill chunks wider than 256 rows) when a
  * model too large to be held twice keeps its projection weights K-tile-major only */
@@ -527,12 +504,6 @@ int lade_splitk_reduce(const float* part, void* C, int64_t ldc, int32_t M, int32
 
 /* ---- misc ------------------------------------------------------------------------------- */
 int lade_version(void);
-/* what this build of the library contains: bit 0 = the experimental kernels (`make EXPERIMENTAL=1`): the attention forms with RoPE + KV append
- * inside the launch (lade_attn_args.n_parts > 0, sync_flags), lade_gemm_ra_kt, the ping-pong K loop of lade_gemm_skinny* (ring >= 10), its
- * 16-row-granular tiles (mt = 16) - all
- * bit-identical or within rounding of the default forms, all measured slower or equal at every BASELINE shape; the default build answers
- * them with LADE_E_ARG */
-int lade_build_flags(void);
 const char* lade_last_error_string(void);
 /* kernel timing helper for bench.py: runs `reps` launches of lade_attn_fwd (+combine) on `stream`
  * bracketed by hipEvents and returns the mean duration of one launch pair in microseconds. */

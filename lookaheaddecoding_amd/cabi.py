@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LADE_HIP_LIB") or os.path.join(_HERE, "liblade_hip.so")     # env override: kernel experiments
 
-ABI_VERSION = 3           # LADE_ABI_VERSION of include/lade_hip.h this binding was written against (checked at load time)
+ABI_VERSION = 4           # LADE_ABI_VERSION of include/lade_hip.h this binding was written against (checked at load time)
 LADE_BF16, LADE_F16, LADE_F32 = 0, 1, 2
 DTYPE_CODE = {torch.bfloat16: LADE_BF16, torch.float16: LADE_F16, torch.float32: LADE_F32}
 
@@ -57,10 +57,7 @@ class AttnArgs(C.Structure):
                 ("q_row_stride", C.c_int64), ("out_row_stride", C.c_int64),
                 ("H", C.c_int32), ("Hkv", C.c_int32), ("d", C.c_int32), ("S_max", C.c_int32),
                 ("dtype", C.c_int32), ("n_splits", C.c_int32), ("scale", C.c_float), ("mask", MaskParams),
-                # ABI 2: work-group shape + fused RoPE / KV append (all zero = the ABI-1 behaviour)
-                ("wg_rows", C.c_int32), ("n_parts", C.c_int32), ("qkv_parts", C.c_void_p), ("part_stride", C.c_int64),
-                ("positions", C.c_void_p), ("cos_tab", C.c_void_p), ("sin_tab", C.c_void_p), ("max_pos", C.c_int32),
-                ("sync_flags", C.c_void_p)]
+                ("wg_rows", C.c_int32)]            # ABI 2: work-group shape (0 = the ABI-1 behaviour)
 
 
 class QkvEpilogue(C.Structure):
@@ -119,7 +116,6 @@ SIGNATURES = {
     "lade_gather_rows": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "lade_gemm_skinny": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "lade_gemm_skinny_kt": [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "lade_gemm_ra_kt": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "lade_weight_to_ktile": [_vp, _i64, _vp, _i32, _i32, _i32, _vp],
     "lade_weight_from_ktile": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "lade_add_rmsnorm_parts": [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
@@ -131,7 +127,6 @@ SIGNATURES = {
     "lade_splitk_reduce": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
     "lade_record_seal": [C.POINTER(C.c_uint32), C.c_uint32],
     "lade_version": [],
-    "lade_build_flags": [],
     "lade_last_error_string": [],
     "lade_time_attn": [C.POINTER(AttnArgs), _i32, C.POINTER(C.c_float), _vp],
     "lade_time_attn_rot": [C.POINTER(AttnArgs), _i32, _i32, C.POINTER(C.c_float), _vp],
@@ -172,7 +167,7 @@ def debug(name: str, default=None):
     """One experiment switch of `LADE_DEBUG=name[=value],name2[=value2],...` (read at every call: tests flip them at run time): the kernel
     ablation bits and tuner experiments that only tools/ and A/B runs use - gemm_dbg, attn_dbg, attn_shape, attn_splits, attn_split_rule,
     combine_hpb (those six are read by the library itself), tune_consumer, gu_tail_fixed, tune_ring, tune_verbose, attn_tune, row_classes,
-    draw_torch, fuse_tail, fuse_rope, poll_reads_per_yield.  A bare name means "1"."""
+    draw_torch, fuse_tail, poll_reads_per_yield.  A bare name means "1"."""
     s = os.environ.get("LADE_DEBUG")
     if not s:
         return default
@@ -181,11 +176,6 @@ def debug(name: str, default=None):
         if k == name:
             return v if v != "" else "1"
     return default
-
-
-def experimental() -> bool:
-    """whether the loaded library was built with -DLADE_EXPERIMENTAL (the attention forms with RoPE + KV append inside the launch)"""
-    return bool(lib().lade_build_flags() & 1)
 
 
 def stream_ptr() -> int:

@@ -40,6 +40,10 @@
 
 namespace lade {
 
+// (the launch functions read lade_attn_args field by field; its size is pinned here and in tests/test_cabi_symbols.py so that the header and
+// cabi.AttnArgs cannot drift apart)
+static_assert(sizeof(lade_attn_args) == 144, "lade_attn_args: layout of ABI version 4");
+
 struct AttnK {
     const uint16_t* q;
     const uint16_t* k;
@@ -57,19 +61,6 @@ struct AttnK {
     float inv_T;        // 1 / T, rounded once on the host
     int n_groups;       // row blocks x KV heads
     lade_mask_params m;
-    // fused RoPE + KV append (kernels with NPC > 0): q and the step's new K / V rows come from the qkv projection's fp32 split-K partials
-    const float* parts;          // [n_parts][T][row_w], part_stride elements apart
-    size_t part_stride;
-    const int32_t* positions;    // [T] or null (= table row t)
-    const uint16_t* cos_tab;     // [max_pos][D]
-    const uint16_t* sin_tab;
-    uint16_t* k_w;               // the caches again, writable
-    uint16_t* vt_w;
-    int n_parts, max_pos, row_w;
-    // producer mode of the fused form (sync_flags given): the first n_prod work-groups of the grid do lade_rope_kv_append_parts' work ONCE per KV head
-    // (32 tokens each) and raise flags[kvh]; the attention work-groups of that head request the cache tiles that hold no new row, then wait for the flag
-    int32_t* flags;
-    int n_prod, prod_chunks;
 };
 
 // ---- 1-D grid, XCD aware ---------------------------------------------------------------------------------------------------------
@@ -84,7 +75,7 @@ __device__ __forceinline__ uint32_t div_magic(uint32_t x, uint32_t magic) { retu
 
 struct BlockId { int rb, kvh, sp, group; bool live; };
 __device__ __forceinline__ BlockId block_decode(const AttnK& a) {
-    const uint32_t b = blockIdx.x - (uint32_t)a.n_prod;          // (n_prod is a multiple of 8: b mod 8 = the XCD of the block stays what it was)
+    const uint32_t b = blockIdx.x;
     const uint32_t x = b & 7u, j = b >> 3;
     const uint32_t q = div_magic(j, a.ns_magic);
     BlockId r;
@@ -250,151 +241,6 @@ __device__ __forceinline__ void dbg_stamp(const AttnK& a, int slot) {
 __device__ __forceinline__ void dbg_stamp(const AttnK&, int) {}
 #endif
 
-// ---- fused RoPE + KV append ------------------------------------------------------------------------------------------------------
-// The qkv projection of a decode step is a split-K GEMM that leaves fp32 partials; round 1-4 summed them, rotated q / k and appended the
-// new K / V rows in a launch of their own (lade_rope_kv_append_parts, 6.4-8.3 us per layer inside a step: latency, not bytes).  With
-// NPC > 0 the attention work-groups do it themselves - the seam is per head, not all-to-all: a work-group of KV head h needs the q rows
-// of its own heads (every split rebuilds them: 30 KB of fp32 per partial at T = 60) and, if its key range reaches into the new rows
-// P .. P+T, exactly those rows of K and V^T - which it writes to the cache (for the steps to come) and then streams back like any other
-// tile.  No work-group ever waits for another one: row blocks that share a KV head write the same bytes.  The arithmetic is
-// lade_rope_kv_append_parts' own, operation for operation (sum in split order from 0, round once, one rounding per torch op of
-// apply_rotary_pos_emb, lade/models/modeling_llama.py:321-346): q, the cache rows and therefore the attention output are bit-identical
-// to the two-launch form (tests/test_gpu_fused_rope.py).
-// One item = 8 + 8 values of one head row: columns i .. i+7 and their rotation partners i + D/2 ..
-// (the cos / sin tables of a rotary embedding are cat(freqs, freqs) - lade/models/modeling_llama.py:252 - so ONE 16-byte load per table
-// serves columns i .. i+7 and i + D/2 ..: the fused form requires such tables, include/lade_hip.h)
-template <int NPC> struct RopeItem { float4 va[NPC][2], vb[NPC][2]; u32x4 c1, s1; };
-
-template <int NPC, int D>
-__device__ __forceinline__ void rope_load(RopeItem<NPC>& it, const AttnK& a, size_t e0, int trow, int i) {
-#pragma unroll
-    for (int j = 0; j < NPC; ++j) {                                       // a partial beyond n_parts re-reads the last one (never added)
-        const float* pa = a.parts + (size_t)min(j, a.n_parts - 1) * a.part_stride + e0;
-        it.va[j][0] = *reinterpret_cast<const float4*>(pa);
-        it.va[j][1] = *reinterpret_cast<const float4*>(pa + 4);
-        it.vb[j][0] = *reinterpret_cast<const float4*>(pa + D / 2);
-        it.vb[j][1] = *reinterpret_cast<const float4*>(pa + D / 2 + 4);
-    }
-    const uint16_t* c = a.cos_tab + (size_t)trow * D + i;
-    const uint16_t* sn = a.sin_tab + (size_t)trow * D + i;
-    it.c1 = *reinterpret_cast<const u32x4*>(c);
-    it.s1 = *reinterpret_cast<const u32x4*>(sn);
-}
-
-__device__ __forceinline__ uint16_t half_of(const u32x4& v, int e) { return (uint16_t)(v[e >> 1] >> ((e & 1) * 16)); }
-
-template <typename T, int NPC>
-__device__ __forceinline__ void rope_apply(const RopeItem<NPC>& it, int n_parts, u32x4& o1, u32x4& o2) {
-    float a[8], b[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { a[e] = 0.f; b[e] = 0.f; }
-#pragma unroll
-    for (int j = 0; j < NPC; ++j)
-        if (j < n_parts) {
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                a[4 * h2] += it.va[j][h2].x; a[4 * h2 + 1] += it.va[j][h2].y; a[4 * h2 + 2] += it.va[j][h2].z; a[4 * h2 + 3] += it.va[j][h2].w;
-                b[4 * h2] += it.vb[j][h2].x; b[4 * h2 + 1] += it.vb[j][h2].y; b[4 * h2 + 2] += it.vb[j][h2].z; b[4 * h2 + 3] += it.vb[j][h2].w;
-            }
-        }
-    uint16_t r1[8], r2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float a1 = Elem<T>::ld(Elem<T>::st(a[e])), a2 = Elem<T>::ld(Elem<T>::st(b[e]));
-        // q*cos + rotate_half(q)*sin, rotate_half = cat(-x2, x1); one rounding per torch op
-        r1[e] = Elem<T>::st(__fadd_rn(rnd<T>(__fmul_rn(a1, Elem<T>::ld(half_of(it.c1, e)))), rnd<T>(__fmul_rn(-a2, Elem<T>::ld(half_of(it.s1, e))))));
-        r2[e] = Elem<T>::st(__fadd_rn(rnd<T>(__fmul_rn(a2, Elem<T>::ld(half_of(it.c1, e)))), rnd<T>(__fmul_rn(a1, Elem<T>::ld(half_of(it.s1, e))))));
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        o1[e] = (uint32_t)r1[2 * e] | ((uint32_t)r1[2 * e + 1] << 16);
-        o2[e] = (uint32_t)r2[2 * e] | ((uint32_t)r2[2 * e + 1] << 16);
-    }
-}
-
-// ---- producer mode of the fused form ---------------------------------------------------------------------------------------------------
-// The first form above makes every KV split of a head rebuild the head's q rows from fp32 partials (+15.6 MB into the start-of-launch
-// burst: measured +3.7 us per layer).  Here lade_rope_kv_append_parts' work is done ONCE - by dedicated work-groups at the head of the
-// grid, one per (KV head, 32 tokens) - and handed to the attention work-groups of that head INSIDE the launch: the producer writes the
-// rotated q rows (to the caller's q buffer), the K rows and the V^T columns with WRITE-THROUGH stores (sc0 sc1: the bytes leave the XCD's
-// L2 as they are issued), drains them (s_waitcnt vmcnt(0) - inline asm, so that the compiler cannot drop it), and bumps flags[kvh]
-// (relaxed, device scope).  A consumer polls the flag from ONE lane (relaxed sc1 loads, s_sleep between them, bounded), passes a
-// barrier and only then requests q and the tiles that hold new rows - with sc1 loads, the consumer side of the guide's
-// {write-through stores / sc1 loads} form (MI355X_MICROARCH.md, inter-workgroup visibility); everything it requested before
-// (the tiles of the cache proper) does not depend on the producers.  Dispatch order is not relied upon for correctness: a consumer whose
-// flag never comes (the producers queued behind a full chip) gives up after ~0.1 s and the launch ends - wrong results instead of
-// a hung GPU; the producers sit at the head of the grid so that in practice they are resident first.  flags[] is reset by
-// lade_attn_combine (this form needs n_splits > 1), so the buffer only has to be zero before the first launch.
-__device__ __forceinline__ void store_wt_b128(void* p, u32x4 v) { asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory"); }
-__device__ __forceinline__ void store_wt_b16(void* p, uint32_t v) { asm volatile("global_store_short %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory"); }
-
-constexpr int PROD_TOK = 32;           // tokens per producer work-group
-
-template <typename T, int D, int NPC, int NTHR>
-__device__ __forceinline__ void rope_producer(const AttnK& a, unsigned char* smem) {
-    constexpr int VPH = D / 16, LDV = D + 2;
-    const int tid = threadIdx.x;
-    const int pb = blockIdx.x;
-    const int kvh = pb / a.prod_chunks, ch = pb - kvh * a.prod_chunks;
-    if (kvh >= a.Hkv) return;                                   // padding of the producer range to a multiple of 8
-    int P = a.m.P;
-    if (a.dyn_P) P = *a.dyn_P;
-    const int t0 = ch * PROD_TOK, nt_ = min(PROD_TOK, a.m.T - t0);
-    const int n_rep = a.n_rep;
-    const bool writes = P + a.m.T <= a.S_max;                   // (a device-side cache length past the cache: nothing is written, as in lade_rope_kv_append)
-    uint16_t* q_out = const_cast<uint16_t*>(a.q);
-    {
-        // q rows of the group's heads + the K row: one item = 8 + 8 values (columns i.., i + D/2..) of one head row.  The q rows are rotated
-        // whatever the cache length (the two-launch form does the same); only the cache stores are skipped past the cache.
-        const int per_tok = (n_rep + 1) * VPH;
-        for (int idx = tid; idx < nt_ * per_tok; idx += NTHR) {
-            const int tt = idx / per_tok, rem = idx - tt * per_tok, hs = rem / VPH, i = (rem - hs * VPH) * 8;
-            const int t = t0 + tt;
-            int trow = t;
-            if (a.positions) { trow = a.positions[t]; trow = trow < 0 ? 0 : (trow >= a.max_pos ? a.max_pos - 1 : trow); }
-            if (hs >= n_rep && !writes) continue;
-            const size_t col = hs < n_rep ? (size_t)(kvh * n_rep + hs) * D : (size_t)(a.H + kvh) * D;
-            RopeItem<NPC> it;
-            rope_load<NPC, D>(it, a, (size_t)t * a.row_w + col + i, trow, i);
-            u32x4 o1, o2;
-            rope_apply<T, NPC>(it, a.n_parts, o1, o2);
-            uint16_t* dst = hs < n_rep ? q_out + (size_t)t * a.q_row_stride + (size_t)(kvh * n_rep + hs) * D + i
-                                       : a.k_w + ((size_t)kvh * a.S_max + P + t) * D + i;
-            store_wt_b128(dst, o1);
-            store_wt_b128(dst + D / 2, o2);
-        }
-    }
-    if (writes) {
-        // V rows: partials summed in split order, rounded once, transposed through LDS ([token][d], padded rows)
-        uint16_t* stage_v = reinterpret_cast<uint16_t*>(smem);
-        const size_t v_col = (size_t)(a.H + a.Hkv + kvh) * D;
-        for (int idx = tid; idx < nt_ * (D / 4); idx += NTHR) {
-            const int tt = idx / (D / 4), d4 = (idx - tt * (D / 4)) * 4;
-            const size_t e0 = (size_t)(t0 + tt) * a.row_w + v_col + d4;
-            float4 vp[NPC];
-#pragma unroll
-            for (int j = 0; j < NPC; ++j) vp[j] = *reinterpret_cast<const float4*>(a.parts + (size_t)min(j, a.n_parts - 1) * a.part_stride + e0);
-            float4 acc = float4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int j = 0; j < NPC; ++j)
-                if (j < a.n_parts) { acc.x += vp[j].x; acc.y += vp[j].y; acc.z += vp[j].z; acc.w += vp[j].w; }
-            uint32_t* dst = reinterpret_cast<uint32_t*>(stage_v + tt * LDV + d4);
-            dst[0] = (uint32_t)from_f32<T>(acc.x) | ((uint32_t)from_f32<T>(acc.y) << 16);
-            dst[1] = (uint32_t)from_f32<T>(acc.z) | ((uint32_t)from_f32<T>(acc.w) << 16);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        wg_barrier();
-        for (int idx = tid; idx < D * PROD_TOK; idx += NTHR) {
-            const int dd = idx / PROD_TOK, tt = idx - dd * PROD_TOK;
-            if (tt < nt_) store_wt_b16(a.vt_w + ((size_t)kvh * D + dd) * a.S_max + P + t0 + tt, stage_v[tt * LDV + dd]);
-        }
-    }
-    // every store of this wave has left the chip's caches; then the barrier; then ONE arrival per work-group
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    wg_barrier();
-    if (tid == 0) __hip_atomic_fetch_add(a.flags + kvh, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Work split inside a work-group of RG x KQ waves: wave (rg, kq) owns query rows [32*rg, 32*rg+32) of the block and the
 // 32-key part kq of every stage; a stage is KQ/2 tiles of 64 keys.  Three shapes are built:
 //   RG=4, KQ=2 (8 waves, 128 rows, stage = 1 tile,  3-stage ring)   steps of more than 64 (head-in-group, token) rows
@@ -406,8 +252,7 @@ __device__ __forceinline__ void rope_producer(const AttnK& a, unsigned char* sme
 // KV split sp of n_splits takes a CONTIGUOUS range of ceil(tiles / n_splits) 64-key tiles (the interleaved assignment sp, sp+n, ...
 // is kept behind LADE_DEBUG=attn_dbg=64: it balances perfectly but loses DRAM locality, +1.6 us at the 7B shape).  The KQ key parts keep
 // separate online-softmax states and are merged through LDS at the end.
-// NPC = 0: q is read from memory and the new K / V rows are already in the cache; NPC = 2 | 4: fused RoPE + KV append from up to NPC partials
-template <typename T, int D, int RG, int KQ, int NPC>
+template <typename T, int D, int RG, int KQ>
 __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
     constexpr int NW = RG * KQ;                    // waves
     constexpr int NTHR = 64 * NW;
@@ -427,13 +272,6 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
     // LDS: [ring of NSTG stages of TPS x (K tile | V^T tile)] [Q tile]; the ring is reused for the merge + store staging
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* q_lds = smem + NSTG * STAGE_BYTES;
-    if constexpr (NPC > 0) {
-        if ((int)blockIdx.x < a.n_prod) {               // producer mode: the head of the grid does the RoPE + append work once per KV head
-            rope_producer<T, D, NPC, NTHR>(a, smem);
-            return;
-        }
-    }
-    const bool pmode = NPC > 0 && a.n_prod > 0;         // ... and this work-group waits for its head's flag before it touches q or a new row
     dbg_stamp(a, 0);
 
     const int tid = threadIdx.x;
@@ -463,22 +301,7 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
     };
     // the Q tile is requested FIRST: its addresses need nothing but the block id, so its pieces are on their way while the cache length
     // (a dependent scalar load in hipGraph steps) is still in flight; the first counted wait covers the Q tile + stage 0 (Q is the oldest)
-    constexpr int VPH = D / 16;                    // fused: 16-byte vector pairs (i, i + D/2) of one head row
-    constexpr int NPI = NPC ? NPC : 1;
-    constexpr int QI = (ROWS * VPH + NTHR - 1) / NTHR;       // fused: rope items of the Q tile per thread
-    RopeItem<NPI> qit[QI];
-    auto q_item = [&](int it, int& row, int& i, int& hg, int& t) -> int {      // 0: nothing, 1: a real row, 2: a padding row of a live 32-row group (zeros)
-        const int idx = tid + it * NTHR;
-        row = idx / VPH;
-        i = (idx - row * VPH) * 8;
-        hg = 0; t = 0;
-        if (idx >= ROWS * VPH) return 0;
-        const int r = rbk * ROWS + row;
-        if (r < n_rows) { split_row(r, hg, t); return 1; }
-        return rbk * ROWS + (row & ~31) < n_rows ? 2 : 0;
-    };
-    auto issue_q = [&](auto sc1_c) {
-        constexpr int AUX = decltype(sc1_c)::value ? 16 : 0;      // sc1: served by L2 / memory, never by this CU's L1 (producer mode)
+    auto issue_q = [&]() {
 #pragma unroll
         for (int i = 0; i < QPW; ++i) {
             const int piece = wave * QPW + i;
@@ -492,24 +315,10 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
             split_row(r, hg, t);
             const uint16_t* src = a.q + (size_t)t * a.q_row_stride + (size_t)(kvh * n_rep + hg) * D + c * 8;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(q_lds + piece * 1024), 16, 0, AUX);
+                                             (__attribute__((address_space(3))) void*)(q_lds + piece * 1024), 16, 0, 0);
         }
     };
-    if constexpr (NPC == 0) {
-        issue_q(std::false_type{});
-    } else if (!pmode) {
-        // fused: the q rows of this block as fp32 partials of the qkv projection + their cos / sin rows, requested before anything that
-        // depends on the cache length; rotated and written to the Q tile further down, behind the K / V requests
-#pragma unroll
-        for (int it = 0; it < QI; ++it) {
-            int row, i, hg, t;
-            if (q_item(it, row, i, hg, t) == 1) {
-                int trow = t;
-                if (a.positions) { trow = a.positions[t]; trow = trow < 0 ? 0 : (trow >= a.max_pos ? a.max_pos - 1 : trow); }
-                rope_load<NPI, D>(qit[it], a, (size_t)t * a.row_w + (size_t)(kvh * n_rep + hg) * D + i, trow, i);
-            }
-        }
-    }
+    issue_q();
     // ---- split geometry: split sp covers the 64-key tiles base, base+stride, ... (my_tiles of them)
     lade_mask_params m = a.m;
     if (a.dyn_P) m.P = *a.dyn_P;
@@ -542,11 +351,9 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
         unsigned char* ks = smem + stage * STAGE_BYTES + ts * TILE_BYTES;
         kv.template issue<AUX>(kbytes + (size_t)k0 * D * 2, vbytes + (size_t)k0 * 2, ks, ks + K_BYTES);
     };
-    int sc1_from_q = 1 << 30;            // producer mode: tiles (offsets within the split) from this one on hold rows a producer wrote in THIS launch: sc1 loads
     // cache policy of the K / V stream: a COMPILE-time constant (LADE_KV_AUX; bits 1 = sc0, 2 = nt, 16 = sc1) - variants are separate builds
     auto issue_tiles = [&](int stage, int ts, int tile) {
-        if (NPC > 0 && tile - base >= sc1_from_q) issue_tiles_aux(stage, ts, tile, std::integral_constant<int, 16>{});
-        else issue_tiles_aux(stage, ts, tile, std::integral_constant<int, LADE_KV_AUX>{});
+        issue_tiles_aux(stage, ts, tile, std::integral_constant<int, LADE_KV_AUX>{});
     };
     const int nt = (my_tiles + TPS - 1) / TPS;                                  // stages
     const int nt_issued = max(nt, NSTG);                                        // the first NSTG stages are always in flight
@@ -557,167 +364,8 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
 #pragma unroll
         for (int ts = 0; ts < TPS; ++ts) issue_tiles(stage, ts, tile_of(j, ts));
     };
-    float pm_poison = 0.f;               // producer mode: NaN once this work-group's wait for its producers has timed out
-    bool pm_wait_all = false;            // producer mode: q was requested AFTER the first stages - the loop's first wait covers everything
-    int store_fence_at = -1;             // fused: the loop iteration behind which the first tile holding a row this work-group stored is requested
-    if constexpr (NPC == 0) {
 #pragma unroll
-        for (int s = 0; s < NSTG; ++s) issue_stage(s, s);
-    } else {
-        // ---- fused RoPE + KV append ----
-        if (pmode) {
-            // producer mode: the ring stages that hold no new row are requested at once; q and the others after this KV head's flag
-            const int first_new_q = m.P / KT - base;       // tile (within the split) of the first new key; <= 0: the split starts inside the new rows
-            int early = 0;
-#pragma unroll
-            for (int s = 0; s < NSTG; ++s) {
-                const int last_q = s * TPS < my_tiles ? min(s * TPS + TPS - 1, my_tiles - 1) : 0;
-                if (early == s && last_q < first_new_q) early = s + 1;
-            }
-            if (early == NSTG) {
-#pragma unroll
-                for (int s = 0; s < NSTG; ++s) issue_stage(s, s);
-            } else {
-                for (int s = 0; s < early; ++s) issue_stage(s, s);
-            }
-            if (tid == 0) {                          // ONE lane polls (relaxed, device scope: an sc1 load), bounded: ~0.1 s
-                int spins = 0;
-                while (__hip_atomic_load(a.flags + kvh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a.prod_chunks && ++spins < (1 << 20)) __builtin_amdgcn_s_sleep(2);
-                *reinterpret_cast<volatile int*>(q_lds) = spins >= (1 << 20);
-            }
-            wg_barrier();
-            // a poll that ran out must not end as plausible numbers: the work-group's row sums become NaN, and with them the merged output rows
-            // (the Q tile is free until issue_q below: the word is read by every thread between two barriers)
-            if (*reinterpret_cast<volatile int*>(q_lds)) pm_poison = __builtin_nanf("");
-            wg_barrier();
-            sc1_from_q = first_new_q;                // from here on the tiles that hold new rows are requested with sc1 loads
-            issue_q(std::true_type{});
-            for (int s = early; s < NSTG; ++s) issue_stage(s, s);
-            pm_wait_all = true;
-        } else {
-        // the rows P .. P+T of K and V^T that fall into this work-group's key range are its own to produce: key k_lo .. k_hi
-        const int k_lo = max(m.P, base * KT), k_hi = min(S_tot, (base + my_tiles) * KT);
-        const int n_new = S_tot <= a.S_max ? max(0, k_hi - k_lo) : 0;         // (a device-side cache length past the cache: nothing is written, as in lade_rope_kv_append)
-        const int t_lo = k_lo - m.P;
-        auto q_finish = [&]() {                  // rotate the q rows and write them to the Q tile (swizzled like the DMA would have)
-#pragma unroll
-            for (int it = 0; it < QI; ++it) {
-                int row, i, hg, t;
-                const int kind = q_item(it, row, i, hg, t);
-                if (kind == 0) continue;
-                u32x4 o1 = u32x4{0u, 0u, 0u, 0u}, o2 = o1;
-                if (kind == 1) rope_apply<T, NPI>(qit[it], a.n_parts, o1, o2);
-                *reinterpret_cast<u32x4*>(q_lds + tile_off<2 * D>(row, i >> 3)) = o1;
-                *reinterpret_cast<u32x4*>(q_lds + tile_off<2 * D>(row, (i + D / 2) >> 3)) = o2;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // published by the barrier of the loop's first iteration
-        };
-        if (n_new == 0) {
-#pragma unroll
-            for (int s = 0; s < NSTG; ++s) issue_stage(s, s);
-            q_finish();
-        } else {
-            constexpr int CH = 16 * RG;                      // new K / V rows per pass
-            constexpr int KI = (CH * VPH + NTHR - 1) / NTHR; // rope items of a pass per thread
-            constexpr int VS = CH * (D / 4) / NTHR;          // float4 sites of a pass's V rows per thread
-            constexpr int LDV = D + 2;                       // row stride (elements) of the V staging tile [CH][D]: it lives in the Q tile
-            static_assert(VS >= 1 && (CH * (D / 4)) % NTHR == 0 && CH * LDV * 2 <= Q_BYTES, "V staging pass");
-            const size_t k_col = (size_t)(a.H + kvh) * D, v_col = (size_t)(a.H + a.Hkv + kvh) * D;
-            RopeItem<NPI> kit[KI];
-            float4 vpart[NPI][VS];
-            auto kv_load = [&](int c) {
-#pragma unroll
-                for (int it = 0; it < KI; ++it) {
-                    const int idx = tid + it * NTHR, tt = idx / VPH, i = (idx - tt * VPH) * 8;
-                    if (idx < CH * VPH && c * CH + tt < n_new) {
-                        const int t = t_lo + c * CH + tt;
-                        int trow = t;
-                        if (a.positions) { trow = a.positions[t]; trow = trow < 0 ? 0 : (trow >= a.max_pos ? a.max_pos - 1 : trow); }
-                        rope_load<NPI, D>(kit[it], a, (size_t)t * a.row_w + k_col + i, trow, i);
-                    }
-                }
-#pragma unroll
-                for (int sv = 0; sv < VS; ++sv) {
-                    const int idx = tid + sv * NTHR, tt = idx / (D / 4), d4 = (idx - tt * (D / 4)) * 4;
-                    if (c * CH + tt < n_new) {
-                        const size_t e0 = (size_t)(t_lo + c * CH + tt) * a.row_w + v_col + d4;
-#pragma unroll
-                        for (int j = 0; j < NPI; ++j) vpart[j][sv] = *reinterpret_cast<const float4*>(a.parts + (size_t)min(j, a.n_parts - 1) * a.part_stride + e0);
-                    }
-                }
-            };
-            auto kv_store = [&](int c, uint16_t* stage_v) {
-                // V: partials summed in split order, rounded once, staged [token][d] ...
-#pragma unroll
-                for (int sv = 0; sv < VS; ++sv) {
-                    const int idx = tid + sv * NTHR, tt = idx / (D / 4), d4 = (idx - tt * (D / 4)) * 4;
-                    if (c * CH + tt < n_new) {
-                        float4 acc = float4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int j = 0; j < NPI; ++j)
-                            if (j < a.n_parts) { acc.x += vpart[j][sv].x; acc.y += vpart[j][sv].y; acc.z += vpart[j][sv].z; acc.w += vpart[j][sv].w; }
-                        uint32_t* dst = reinterpret_cast<uint32_t*>(stage_v + tt * LDV + d4);
-                        dst[0] = (uint32_t)from_f32<T>(acc.x) | ((uint32_t)from_f32<T>(acc.y) << 16);
-                        dst[1] = (uint32_t)from_f32<T>(acc.z) | ((uint32_t)from_f32<T>(acc.w) << 16);
-                    }
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                wg_barrier();
-                // K: rotated rows straight to cache row P + t
-#pragma unroll
-                for (int it = 0; it < KI; ++it) {
-                    const int idx = tid + it * NTHR, tt = idx / VPH, i = (idx - tt * VPH) * 8;
-                    if (idx < CH * VPH && c * CH + tt < n_new) {
-                        u32x4 o1, o2;
-                        rope_apply<T, NPI>(kit[it], a.n_parts, o1, o2);
-                        uint16_t* dst = a.k_w + ((size_t)kvh * a.S_max + k_lo + c * CH + tt) * D + i;
-                        *reinterpret_cast<u32x4*>(dst) = o1;
-                        *reinterpret_cast<u32x4*>(dst + D / 2) = o2;
-                    }
-                }
-                // ... and written transposed, the token index fastest: V^T[d][P + t]
-                for (int idx = tid; idx < D * CH; idx += NTHR) {
-                    const int dd = idx / CH, tt = idx - dd * CH;
-                    if (c * CH + tt < n_new) a.vt_w[((size_t)kvh * D + dd) * a.S_max + k_lo + c * CH + tt] = stage_v[tt * LDV + dd];
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                wg_barrier();                  // the staging tile is free again (next pass, or the q rows)
-            };
-            // the stages that hold none of those rows are requested now, the others once the rows are in memory
-            const int first_new_q = m.P / KT - base;       // tile (within the split) of the first new key; <= 0: the split starts inside the new rows
-            int early = 0;
-#pragma unroll
-            for (int s = 0; s < NSTG; ++s) {
-                const int last_q = s * TPS < my_tiles ? min(s * TPS + TPS - 1, my_tiles - 1) : 0;
-                if (early == s && last_q < first_new_q) early = s + 1;
-            }
-            const int n_pass = (n_new + CH - 1) / CH;
-            if (early == NSTG) {
-                // the usual case: the new rows lie behind the first NSTG stages.  Straight-line code: the partials are requested BEFORE the
-                // stages, so the counted wait the compiler derives for them leaves every DMA piece in flight.  The V staging tile lives in
-                // the Q tile, which is written last.
-                kv_load(0);
-#pragma unroll
-                for (int s = 0; s < NSTG; ++s) issue_stage(s, s);
-                kv_store(0, reinterpret_cast<uint16_t*>(q_lds));
-                for (int c = 1; c < n_pass; ++c) { kv_load(c); kv_store(c, reinterpret_cast<uint16_t*>(q_lds)); }
-                q_finish();
-                // the stores must have landed before the first stage that holds one of those rows is requested: checked in the loop, where
-                // that request is made (a wait here would also wait for the stages in flight)
-                store_fence_at = max(NSTG, first_new_q / TPS) - NSTG;
-            } else {
-                // a split that reaches the new rows within its first NSTG stages (short caches): nothing is requested before the rows are in
-                // memory; the q rows go first (their registers are free for the passes), the V staging tile lives in the idle ring
-                q_finish();
-                for (int c = 0; c < n_pass; ++c) { kv_load(c); kv_store(c, reinterpret_cast<uint16_t*>(smem)); }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                wg_barrier();
-#pragma unroll
-                for (int s = 0; s < NSTG; ++s) issue_stage(s, s);
-            }
-        }
-        }
-    }
+    for (int s = 0; s < NSTG; ++s) issue_stage(s, s);
     dbg_stamp(a, 1);
 
     // this lane's query row (overlaps the DMA flight)
@@ -735,7 +383,7 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
     for (int i = 0; i < DBLK; ++i)
 #pragma unroll
         for (int j = 0; j < 16; ++j) oacc[i][j] = 0.f;
-    float m_run = NEG_BIG, l_run = pm_poison;
+    float m_run = NEG_BIG, l_run = 0.f;
     const int krow = 32 * kh + kappa(ql);          // LDS row (key within the tile) of this lane's MFMA row
 
     for (int i = 0; i < nt; ++i) {
@@ -744,8 +392,7 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
         const unsigned char* vs = ks + K_BYTES;
         // wait for stage i (and, the first time, the older Q pieces): the pieces of the younger stages stay in flight
         const int younger = min(nt_issued, i + NSTG) - (i + 1);
-        if (NPC > 0 && pm_wait_all && i == 0) wait_vm<0>();
-        else if (younger >= 2) wait_vm<2 * PIECES>();
+        if (younger >= 2) wait_vm<2 * PIECES>();
         else if (younger == 1) wait_vm<PIECES>();
         else wait_vm<0>();
         wg_barrier();
@@ -809,11 +456,6 @@ __global__ __launch_bounds__(64 * RG * KQ) void attn_fwd_kernel(AttnK a) {
         }
         if (i + NSTG < nt) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if constexpr (NPC > 0) {
-                // fused: this work-group's own K / V rows have reached memory before a stage that holds them is requested (once per launch,
-                // work-group uniform; every wave waits for its own stores, the barrier covers the others')
-                if (i == store_fence_at) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
             wg_barrier();              // every wave is done reading this stage
             issue_stage(i + NSTG, stage);
         }
@@ -986,11 +628,6 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(AttnK a, int D) {
     ld.po_stride = (size_t)Tn * a.H * D;
     const u32x4 wv = merge_splits<T>(a.n_splits, ld);
     *reinterpret_cast<u32x4*>(a.out + (size_t)t * a.out_row_stride + (size_t)qh * D + d0) = wv;
-    // producer mode of the fused form: every attention work-group of the launch before this one is done - the flags are zero again for the next
-    if (a.flags && blockIdx.x == 0 && blockIdx.y == 0) {
-        const int lt = threadIdx.y * blockDim.x + threadIdx.x;
-        if (lt < a.Hkv) a.flags[lt] = 0;
-    }
 }
 
 // ---- fp32 path: plain VALU kernel (parity / tiny models; not a BASELINE dtype) -------------
@@ -1050,7 +687,7 @@ __global__ __launch_bounds__(64) void attn_fwd_f32_kernel(AttnF32 a) {
 
 static int validate(const lade_attn_args* a) {
     LADE_REQUIRE(a != nullptr, LADE_E_ARG, "lade_attn: null args");
-    LADE_REQUIRE((a->q || a->n_parts != 0) && a->k_cache && a->vt_cache && a->out, LADE_E_ARG, "lade_attn: null tensor pointer");
+    LADE_REQUIRE(a->q && a->k_cache && a->vt_cache && a->out, LADE_E_ARG, "lade_attn: null tensor pointer");
     LADE_REQUIRE(a->H > 0 && a->Hkv > 0 && a->H % a->Hkv == 0, LADE_E_ARG, "lade_attn: H=%d Hkv=%d", a->H, a->Hkv);
     LADE_REQUIRE(a->mask.T > 0 && a->mask.P >= 0, LADE_E_ARG, "lade_attn: T=%d P=%d", a->mask.T, a->mask.P);
     LADE_REQUIRE(a->S_max % 64 == 0 && a->mask.P + a->mask.T <= a->S_max, LADE_E_ARG,
@@ -1058,18 +695,6 @@ static int validate(const lade_attn_args* a) {
     LADE_REQUIRE(a->n_splits >= 1 && a->n_splits <= 32, LADE_E_ARG, "lade_attn: n_splits=%d (1..32)", a->n_splits);
     LADE_REQUIRE(a->n_splits == 1 || (a->part_o && a->part_ml), LADE_E_ARG, "lade_attn: split-KV needs partial buffers");
     LADE_REQUIRE(a->wg_rows == 0 || a->wg_rows == 32 || a->wg_rows == 64 || a->wg_rows == 128, LADE_E_ARG, "lade_attn: wg_rows=%d (0, 32, 64, 128)", a->wg_rows);
-    if (a->n_parts != 0) {
-        LADE_REQUIRE(a->n_parts >= 1 && a->n_parts <= 4, LADE_E_LIMIT, "lade_attn: fused RoPE takes 1..4 split-K partials, got %d", a->n_parts);
-        LADE_REQUIRE(a->qkv_parts && a->cos_tab && a->sin_tab && a->max_pos > 0, LADE_E_ARG, "lade_attn: fused RoPE needs qkv_parts, cos_tab, sin_tab, max_pos");
-        LADE_REQUIRE(a->positions || a->max_pos >= a->mask.T, LADE_E_ARG, "lade_attn: fused RoPE without positions reads table rows 0..T-1 (max_pos=%d, T=%d)", a->max_pos, a->mask.T);
-        LADE_REQUIRE(a->dtype == LADE_BF16 || a->dtype == LADE_F16, LADE_E_DTYPE, "lade_attn: fused RoPE is built for bf16 / f16 (dtype=%d)", a->dtype);
-        LADE_REQUIRE(a->part_stride >= (int64_t)a->mask.T * (a->H + 2 * a->Hkv) * a->d, LADE_E_ARG, "lade_attn: part_stride %lld is shorter than one partial", (long long)a->part_stride);
-        LADE_REQUIRE(!a->sync_flags || a->Hkv <= 256, LADE_E_LIMIT, "lade_attn: the producer mode's flags are reset by one 256-thread block of lade_attn_combine: Hkv=%d > 256", a->Hkv);
-        LADE_REQUIRE(!a->sync_flags || (a->q && a->n_splits > 1 && a->q_row_stride % 8 == 0), LADE_E_ARG,
-                     "lade_attn: the producer mode of the fused RoPE (sync_flags) writes the rotated q rows to `q` and is reset by lade_attn_combine: it needs q and n_splits > 1");
-    } else {
-        LADE_REQUIRE(!a->sync_flags, LADE_E_ARG, "lade_attn: sync_flags without the fused RoPE (n_parts = 0)");
-    }
     if (!a->mask.is_prefill) {
         const lade_mask_params& m = a->mask;
         LADE_REQUIRE(m.s >= 0 && m.gs > 0 && m.lguess >= 0 && m.lguess % m.gs == 0 && m.level_offset >= 0 && m.dist_offset >= 0,
@@ -1099,59 +724,37 @@ static AttnK make_k(const lade_attn_args* a) {
     k.scale_log2 = a->scale * 1.4426950408889634f;
     { static int dbg = -1; if (dbg < 0) dbg = debug_int("attn_dbg"); k.dbg = dbg; }
     k.m = a->mask;
-    k.parts = a->qkv_parts; k.part_stride = (size_t)a->part_stride; k.positions = a->positions;
-    k.cos_tab = (const uint16_t*)a->cos_tab; k.sin_tab = (const uint16_t*)a->sin_tab;
-    k.k_w = (uint16_t*)a->k_cache; k.vt_w = (uint16_t*)a->vt_cache;
-    k.n_parts = a->n_parts; k.max_pos = a->max_pos; k.row_w = (a->H + 2 * a->Hkv) * a->d;
-    k.flags = a->n_parts ? a->sync_flags : nullptr;
-    k.prod_chunks = cdiv(a->mask.T, PROD_TOK);
-    k.n_prod = k.flags ? 8 * cdiv(a->Hkv * k.prod_chunks, 8) : 0;
     return k;
 }
 
-template <typename T, int D, int RG, int KQ, int NPC>
+template <typename T, int D, int RG, int KQ>
 static int launch_fwd_shape(const lade_attn_args* a, hipStream_t st) {
     AttnK k = make_k(a);
     const int n_rep = a->H / a->Hkv;
     constexpr int ROWS = 32 * RG, TPS = KQ / 2, NSTG = TPS == 1 ? 3 : 2;
     k.n_groups = cdiv(n_rep * a->mask.T, ROWS) * a->Hkv;
-    dim3 grid(k.n_prod + 8 * cdiv(k.n_groups, 8) * a->n_splits);       // [producers |] block_decode: b = x + 8 (q n_splits + sp), group = x + 8 q
+    dim3 grid(8 * cdiv(k.n_groups, 8) * a->n_splits);       // block_decode: b = x + 8 (q n_splits + sp), group = x + 8 q
     const size_t lds = (size_t)KT * D * 2 * 2 * TPS * NSTG + (size_t)ROWS * D * 2;
     static bool attr_set = false;          // > 64 KiB of dynamic LDS needs the opt-in once per kernel
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<T, D, RG, KQ, NPC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<T, D, RG, KQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    hipLaunchKernelGGL((attn_fwd_kernel<T, D, RG, KQ, NPC>), grid, dim3(64 * RG * KQ), lds, st, k);
+    hipLaunchKernelGGL((attn_fwd_kernel<T, D, RG, KQ>), grid, dim3(64 * RG * KQ), lds, st, k);
     return check_launch("lade_attn_fwd");
 }
 
 // The work-group shape is a launch parameter (lade_attn_args.wg_rows: 128 | 64 | 32 query rows of the (head-in-group, token) space per
 // work-group; 0 = 128): which one is fastest depends on the rows per KV head, the split count and the cache length, so the caller's autotune
 // decides it per launch shape inside a step, like the GEMM configurations (StepEngine._refine_attn).  LADE_DEBUG=attn_shape=<rows> forces one (experiments).
-template <typename T, int D, int NPC>
-static int launch_fwd_npc(const lade_attn_args* a, hipStream_t st) {
+template <typename T, int D>
+static int launch_fwd(const lade_attn_args* a, hipStream_t st) {
     static int forced = -1;
     if (forced < 0) forced = debug_int("attn_shape");
     const int shape = forced ? forced : (a->wg_rows ? a->wg_rows : 128);
-    if (shape == 32) return launch_fwd_shape<T, D, 1, 4, NPC>(a, st);
-    // (fused RoPE from 3 or 4 partials: two q items of four partials each + a pass of K / V rows do not fit the 128-row shape's
-    // register file - 359 spilled registers -, so a 128-row request runs as 64-row blocks)
-    if (shape == 64 || NPC > 2) return launch_fwd_shape<T, D, 2, 4, NPC>(a, st);
-    if constexpr (NPC <= 2) return launch_fwd_shape<T, D, 4, 2, NPC>(a, st);
-    return LADE_E_LIMIT;
-}
-
-template <typename T, int D>
-static int launch_fwd(const lade_attn_args* a, hipStream_t st) {
-    if (a->n_parts == 0) return launch_fwd_npc<T, D, 0>(a, st);
-#ifdef LADE_EXPERIMENTAL
-    // RoPE + KV append inside the attention launch (two forms, both bit-identical to the two-launch form and both measured SLOWER at every
-    // BASELINE shape: DESIGN 4.9, profiles/r5_fused_rope_ab.txt): built only with -DLADE_EXPERIMENTAL (make EXPERIMENTAL=1)
-    return a->n_parts <= 2 ? launch_fwd_npc<T, D, 2>(a, st) : launch_fwd_npc<T, D, 4>(a, st);
-#else
-    LADE_REQUIRE(false, LADE_E_ARG, "lade_attn: the fused RoPE + KV append forms (n_parts > 0) are not in this build (make EXPERIMENTAL=1; lade_build_flags() bit 0)");
-#endif
+    if (shape == 32) return launch_fwd_shape<T, D, 1, 4>(a, st);
+    if (shape == 64) return launch_fwd_shape<T, D, 2, 4>(a, st);
+    return launch_fwd_shape<T, D, 4, 2>(a, st);
 }
 
 }  // namespace lade
@@ -1177,7 +780,7 @@ extern "C" int lade_attn_fwd(const lade_attn_args* a, void* stream) {
     }
     LADE_REQUIRE(a->dtype == LADE_BF16 || a->dtype == LADE_F16, LADE_E_DTYPE, "lade_attn_fwd: dtype=%d", a->dtype);
     LADE_REQUIRE(a->d == 128 || a->d == 64, LADE_E_DTYPE, "lade_attn_fwd: head_dim %d (MFMA kernel supports 64 and 128)", a->d);
-    LADE_REQUIRE((a->n_parts != 0 || a->q_row_stride % 8 == 0) && a->out_row_stride % 8 == 0, LADE_E_ARG, "lade_attn_fwd: row strides must keep 16-B alignment");
+    LADE_REQUIRE(a->q_row_stride % 8 == 0 && a->out_row_stride % 8 == 0, LADE_E_ARG, "lade_attn_fwd: row strides must keep 16-B alignment");
     if (a->dtype == LADE_BF16) return a->d == 128 ? launch_fwd<BF16, 128>(a, st) : launch_fwd<BF16, 64>(a, st);
     return a->d == 128 ? launch_fwd<F16, 128>(a, st) : launch_fwd<F16, 64>(a, st);
 }

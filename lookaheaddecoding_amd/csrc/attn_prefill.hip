@@ -265,7 +265,6 @@ extern "C" int lade_attn_prefill(const lade_attn_args* a, void* stream) {
     LADE_REQUIRE(a->dtype == LADE_BF16 || a->dtype == LADE_F16, LADE_E_ARG, "lade_attn_prefill: dtype=%d (bf16 and f16 only; fp32 chunks run on lade_attn_fwd)", a->dtype);
     LADE_REQUIRE(a->d == 128 || a->d == 64, LADE_E_ARG, "lade_attn_prefill: head_dim %d (64 and 128)", a->d);
     LADE_REQUIRE(a->mask.is_prefill == 1, LADE_E_ARG, "lade_attn_prefill: is_prefill=%d (plain causal chunks only; lookahead steps run on lade_attn_fwd)", a->mask.is_prefill);
-    LADE_REQUIRE(a->n_parts == 0 && !a->sync_flags, LADE_E_ARG, "lade_attn_prefill: n_parts=%d (no fused RoPE form: q and the new K / V rows must be in place)", a->n_parts);
     LADE_REQUIRE(a->dyn_P == nullptr, LADE_E_ARG, "lade_attn_prefill: dyn_P is not supported (the block lengths are decided on the host)");
     LADE_REQUIRE(a->H > 0 && a->Hkv > 0 && a->H % a->Hkv == 0, LADE_E_ARG, "lade_attn_prefill: H=%d Hkv=%d", a->H, a->Hkv);
     LADE_REQUIRE(a->mask.T > 0 && a->mask.P >= 0, LADE_E_ARG, "lade_attn_prefill: T=%d P=%d", a->mask.T, a->mask.P);

@@ -23,30 +23,12 @@ struct GemmK {
                            // 2 = row argmax: no C, Cpart holds one (value, column) pair per row and column block
 };
 
-// register-resident-activation kernel (gemm_ra.hpp)
-struct GemmRA {
-    const uint16_t* A;     // [M][lda]
-    const uint16_t* W;     // K-tile-major [K/64][N][64]
-    float* Cpart;          // [n_split][M][N] fp32
-    int64_t lda;
-    int M, N, K;
-    int n_split, tps;      // K tiles per split (<= KT; the last split may hold fewer)
-    int n_groups;          // column groups per split; grid = n_groups * n_split work-groups
-    int dbg;               // 1 = no stores, 4 = no fragment reads / MFMA (tools)
-};
+// what a group of the shape table answers when the wave grid is not one of its shapes: outside the LADE_E_* range (<= 0), so that a real
+// failure of the launch (LADE_E_ARG: the ring does not fit the LDS; LADE_E_LAUNCH) is never taken for it
+constexpr int GEMM_NOT_IN_TABLE = 1;
 
-constexpr int RA_KT = 20;          // K tiles (64 deep) a work-group of the RA kernel holds in registers: K slices of <= 1280
-int gemm_ra_dispatch_bf16(const GemmRA& g, hipStream_t st, int mw, int cs);
-int gemm_ra_dispatch_f16(const GemmRA& g, hipStream_t st, int mw, int cs);
-
-// launch the kernel built for this wave grid (mw x ng waves compute, mt x nt MFMA tiles each); -1 when it is not in the shape table
+// launch the kernel built for this wave grid (mw x ng waves compute, mt x nt MFMA tiles each); GEMM_NOT_IN_TABLE when it is not in the shape table
 int gemm_dispatch_bf16(const GemmK& g, hipStream_t st, int mw, int mt, int ng, int nt);
 int gemm_dispatch_f16(const GemmK& g, hipStream_t st, int mw, int mt, int ng, int nt);
-// the 16-row-granular form (gemm16.hpp): mt16 16-row activation blocks in every wave, ng waves along N with nt16 16-row weight blocks each
-int gemm16_dispatch_bf16(const GemmK& g, hipStream_t st, int mt16, int ng, int nt16);
-int gemm16_dispatch_f16(const GemmK& g, hipStream_t st, int mt16, int ng, int nt16);
-// the ping-pong form (gemm_pp.hpp): mw x ng = the grid of ONE group of four waves
-int gemm_pp_dispatch_bf16(const GemmK& g, hipStream_t st, int mw, int mt, int ng, int nt);
-int gemm_pp_dispatch_f16(const GemmK& g, hipStream_t st, int mw, int mt, int ng, int nt);
 
 }  // namespace lade

@@ -9,9 +9,9 @@ int gemm_dispatch_f16_p3(const GemmK& g, hipStream_t st, int mw, int mt, int ng,
 
 int gemm_dispatch_f16(const GemmK& g, hipStream_t st, int mw, int mt, int ng, int nt) {
     int rc = gemm_dispatch_f16_p0(g, st, mw, mt, ng, nt);
-    if (rc == -1) rc = gemm_dispatch_f16_p1(g, st, mw, mt, ng, nt);
-    if (rc == -1) rc = gemm_dispatch_f16_p2(g, st, mw, mt, ng, nt);
-    if (rc == -1) rc = gemm_dispatch_f16_p3(g, st, mw, mt, ng, nt);
+    if (rc == GEMM_NOT_IN_TABLE) rc = gemm_dispatch_f16_p1(g, st, mw, mt, ng, nt);
+    if (rc == GEMM_NOT_IN_TABLE) rc = gemm_dispatch_f16_p2(g, st, mw, mt, ng, nt);
+    if (rc == GEMM_NOT_IN_TABLE) rc = gemm_dispatch_f16_p3(g, st, mw, mt, ng, nt);
     return rc;
 }
 }  // namespace lade

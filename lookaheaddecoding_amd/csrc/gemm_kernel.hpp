@@ -428,14 +428,14 @@ static int launch_gemm(const GemmK& g0, hipStream_t st) {
        per wave, 0.75 LDS fragment reads per MFMA, double-buffered 64 KB stages */                                        \
                    SHAPE(TT,2,4,4,2) SHAPE(TT,4,2,2,4)
 
-// -1: no kernel of this group for the wave grid
+// GEMM_NOT_IN_TABLE: no kernel of this group for the wave grid
 template <typename T, int PART>
 static int gemm_dispatch_part(const GemmK& g, hipStream_t st, int mw, int mt, int ng, int nt) {
     if constexpr (PART == 0) { GO_0(T) }
     if constexpr (PART == 1) { GO_1(T) }
     if constexpr (PART == 2) { GO_2(T) }
     if constexpr (PART == 3) { GO_3(T) }
-    return -1;
+    return GEMM_NOT_IN_TABLE;
 }
 #undef GO_0
 #undef GO_1

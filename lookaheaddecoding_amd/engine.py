@@ -174,22 +174,20 @@ class StepEngine(KernelDecisions):
         self._ranked = {}                   # (projection, row class) -> the isolated pass's candidates, fastest first [(ms, cfg | None)]
         self._refined = set()               # row classes whose decisions were re-taken inside the step (_refine_in_step)
         self._refining = False
-        # attention launch parameters per row class: (RoPE + KV append fused into the launch, work-group rows, split mode of ops.choose_splits);
-        # the default until (unless) the in-step pass decides: RoPE + append as a launch of their own (the fused form measured +3.7 us per
-        # layer at the 7B step - every split re-reads the q rows as fp32 partials; LADE_DEBUG=fuse_rope=1 makes it the default, the
-        # in-step pass always tries both), the 128-row shape, the sqrt split rule
+        # attention launch parameters per row class: (0, work-group rows, split mode of ops.choose_splits); the default until (unless) the in-step pass
+        # decides: the 128-row shape, the sqrt split rule.  The leading 0 is where the tables kept "RoPE + KV append inside the launch": those forms
+        # measured slower and were removed; the slot stays so that old and new tune files read alike
         self.attn_cfg = {}
-        fuse_env = cabi.debug("fuse_rope", "0")
-        if fuse_env in ("1", "2") and not cabi.experimental():
-            raise cabi.LadeHipError("LADE_DEBUG=fuse_rope needs a library built with `make -C lookaheaddecoding_amd/csrc EXPERIMENTAL=1` (the fused forms measured slower: DESIGN 4.9)")
+        if cabi.debug("fuse_rope", "0") in ("1", "2"):
+            raise cabi.LadeHipError("LADE_DEBUG=fuse_rope: the fused RoPE + KV append attention forms were removed (measured slower: DESIGN 4.9)")
         # work-group rows of the attention launch: 128, but 64 where eight or more heads share a KV head (Llama-2-70B: 480 rows per KV head at T = 60) -
         # 64 row blocks per launch already fill a quarter of the CUs, the split rule then takes 4 splits instead of 6: the same time in the step (config 5:
         # 24.85 / 24.80 vs 24.84 / 24.79 ms alternating) for 1.85 x instead of 2.25 x the algorithmic HBM bytes (profiles/r6_attn_gqa_sweep.txt, r6_c5_gqa_launch_ab.txt)
-        self.attn_default = (int(fuse_env) if fuse_env in ("1", "2") else 0, 128, 0)
+        self.attn_default = (0, 128, 0)
         if self.H // self.Hkv >= 8:
             for mclass in self.ROW_CLASSES:
                 if (self.H // self.Hkv) * (mclass - 31) > 128:          # every step of the class stacks more than 128 rows on a KV head
-                    self.attn_cfg[mclass] = (self.attn_default[0], 64, 0)
+                    self.attn_cfg[mclass] = (0, 64, 0)
         self.step_tune_log = {}             # row class -> what the in-step pass measured (bench.py prints it)
         self._alloc_workspaces(max_T)
         try:
@@ -391,8 +389,6 @@ class StepEngine(KernelDecisions):
         if self.custom_gemm:
             self.ws_part = torch.empty(16 * 128 * max(qkv_w, 2 * self.inter, self.hidden), dtype=torch.float32, device=dev)
             self.ws_q = torch.empty(max_T, self.H * self.d, dtype=dt, device=dev)
-            if getattr(self, "attn_flags", None) is None:          # producer mode of the fused RoPE: one arrival counter per KV head, zero between launches
-                self.attn_flags = torch.zeros(max(64, self.Hkv), dtype=torch.int32, device=dev)
 
     def grow(self, max_seq: int, max_T: int, keep_rows: int = 0) -> None:
         """Enlarges the KV cache and / or the step workspaces in place (the fused weights stay): the first keep_rows cache
@@ -474,16 +470,12 @@ class StepEngine(KernelDecisions):
         cfg_o = self._tune("wo", T) if fused else None
         cfg_gu = self._tune("wgu", T) if fused else None
         cfg_d = self._tune("wd", T) if fused else None
-        # the attention launch of this row class: RoPE + KV append inside it (from the qkv GEMM's partials) or as a launch of their own,
-        # the work-group shape, the split rule
+        # the attention launch of this row class: the work-group shape, the split rule
         acfg = (self.attn_cfg.get(next(c for c in self.ROW_CLASSES if T <= c), self.attn_default) if fused else (0, 0, 0))
-        if self.has_epilogue and acfg[0]:           # the fused-RoPE attention forms do not carry the qkv epilogue
-            acfg = (0,) + tuple(acfg[1:])
         if n_splits is None:
             n_splits = self.n_splits_for(T, P + T, choice=acfg if fused else None)
         # causal chunks above the last row class (the ones on the library GEMMs): the one-pass prefill kernel instead of the split-KV pair
         pf_attn = use_prefill_attn(T, mask.is_prefill, self.dtype, self.ROW_CLASSES[-1], dyn_P=dyn_P is not None, H=H, Hkv=Hkv, n_cu=self.n_cu)
-        fuse_rope = bool(acfg[0]) and cfg_qkv is not None and cfg_qkv[2] <= 4 and not self.skip_attn
         fuse_embed = cabi.debug("fuse_tail", "1") != "0"      # embedding lookup inside the first layer's input norm (one launch less)
         if not (fuse_embed and self.layers):
             ops.gather_rows(self.embed, ids, out=x, rows=T)
@@ -502,7 +494,7 @@ class StepEngine(KernelDecisions):
             if cfg_qkv:
                 ops.gemm_parts(h, self._w(lw, "wqkv"), part, cfg_qkv[2], cfg_qkv[1], cfg_qkv[0], cfg_qkv[3], cfg_qkv[4], cfg_qkv[5])
                 qb = self.ws_q[:T]
-                if not fuse_rope and self.skip_attn != "all":
+                if self.skip_attn != "all":
                     if lw["epi_parts"] is not None:
                         ops.rope_kv_append_parts_ex(part, cfg_qkv[2], qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d,
                                                     dyn_P=dyn_P, epi=lw["epi_parts"])
@@ -528,16 +520,7 @@ class StepEngine(KernelDecisions):
                     self.attn_events_empty.append((c0, c1))
                 e0 = torch.cuda.Event(enable_timing=True)
                 e0.record()
-            if fuse_rope:
-                # q and the new K / V rows straight from the qkv GEMM's partials: no RoPE launch (same bits as the two-launch form).  Mode 2:
-                # dedicated work-groups of the launch produce them once per KV head and hand them over through sync_flags
-                prod = acfg[0] == 2 and n_splits > 1
-                if prod:
-                    self.attn_flags.zero_()          # (not left to the previous launch's combine: a launch that failed would leave stale arrival counts behind)
-                ops.attn_fwd(qb if prod else None, self.k_cache(li), self.vt_cache(li), mask, H=H, Hkv=Hkv, d=d, out=o, n_splits=n_splits, part_o=self.part_o,
-                             part_ml=self.part_ml, dyn_P=dyn_P, wg_rows=acfg[1], qkv_parts=part, n_parts=cfg_qkv[2], positions=rpos, cos=rcos, sin=rsin,
-                             sync_flags=self.attn_flags if prod else None)
-            elif not self.skip_attn and pf_attn:
+            if not self.skip_attn and pf_attn:
                 # one launch, no partials, no merge: the kernel has no KV split, so `n_splits` (a caller's, or LADE_DEBUG=attn_splits) does not apply
                 ops.attn_prefill(q_in, self.k_cache(li), self.vt_cache(li), mask, H=H, Hkv=Hkv, d=d, out=o)
             elif not self.skip_attn:

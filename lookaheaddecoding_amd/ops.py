@@ -78,60 +78,21 @@ def choose_splits(H: int, n_rep: int, T: int, S_tot: int, n_cu: int = 256, allow
     return (tiles + tps - 1) // tps               # drop the splits that would be empty
 
 
-_HALVES_OK: dict = {}
-
-
-def _check_rope_halves(cos: torch.Tensor, sin: torch.Tensor) -> None:
-    """the fused RoPE loads ONE 16-byte vector per table for columns i.. and i + d/2..: valid for rotary tables built as cat(freqs, freqs)
-    (lade/models/modeling_llama.py:252), which is checked once per table"""
-    key = (cos.data_ptr(), sin.data_ptr(), tuple(cos.shape), cos._version, sin._version)
-    if key not in _HALVES_OK:
-        if torch.cuda.is_current_stream_capturing():
-            return                                # (checked at the eager warm-up that precedes every capture)
-        h = cos.shape[1] // 2
-        if not (torch.equal(cos[:, :h], cos[:, h:]) and torch.equal(sin[:, :h], sin[:, h:])):
-            raise cabi.LadeHipError("fused RoPE needs cos / sin tables whose two halves are equal (emb = cat(freqs, freqs))")
-        if len(_HALVES_OK) > 256:
-            _HALVES_OK.clear()
-        _HALVES_OK[key] = True
-
-
-def attn_fwd(q: Optional[torch.Tensor], k_cache: torch.Tensor, vt_cache: torch.Tensor, mask: StepMask, *, H: int, Hkv: int, d: int,
+def attn_fwd(q: torch.Tensor, k_cache: torch.Tensor, vt_cache: torch.Tensor, mask: StepMask, *, H: int, Hkv: int, d: int,
              out: Optional[torch.Tensor] = None, n_splits: Optional[int] = None, scale: Optional[float] = None,
              q_row_stride: Optional[int] = None, part_o: Optional[torch.Tensor] = None, part_ml: Optional[torch.Tensor] = None,
-             dyn_P: Optional[torch.Tensor] = None, wg_rows: int = 0, qkv_parts: Optional[torch.Tensor] = None, n_parts: int = 0,
-             positions: Optional[torch.Tensor] = None, cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None,
-             sync_flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+             dyn_P: Optional[torch.Tensor] = None, wg_rows: int = 0) -> torch.Tensor:
     """Lookahead attention for one step.  q: [T, >=H*d] rows (token stride q_row_stride elements, default
     q.stride(0)); k_cache [Hkv, S_max, d]; vt_cache [Hkv, d, S_max]; returns out [T, H*d].
-    wg_rows: work-group shape (0 = default, 32 | 64 | 128 query rows per work-group).
-    Fused RoPE + KV append (qkv_parts given): q is not read; q and the new K / V rows P..P+T come from the qkv projection's n_parts (1..4)
-    fp32 split-K partials `qkv_parts` ([>= n_parts][T][(H + 2 Hkv) d] with stride qkv_parts.stride(0), or flat with stride T (H + 2 Hkv) d), rotated with the
-    cos / sin rows positions[t] (positions None: row t) - the rows are written to the caches and the result equals
-    rope_kv_append_parts + attn_fwd bit for bit.  sync_flags (device int32 [>= Hkv], zero before the first launch; needs q = a [T, H*d]
-    buffer and n_splits > 1): the producer mode of the fused form - dedicated work-groups do the RoPE + append work once per KV head
-    and hand it to the attention work-groups inside the launch (include/lade_hip.h)."""
-    for n, t in (("k_cache", k_cache), ("vt_cache", vt_cache)):
+    wg_rows: work-group shape (0 = default, 32 | 64 | 128 query rows per work-group)."""
+    for n, t in (("q", q), ("k_cache", k_cache), ("vt_cache", vt_cache)):
         _dev(t, n)
     T = mask.T
     S_max = k_cache.shape[1]
     assert k_cache.shape == (Hkv, S_max, d) and vt_cache.shape == (Hkv, d, S_max), (k_cache.shape, vt_cache.shape)
     assert k_cache.is_contiguous() and vt_cache.is_contiguous()
     dt = k_cache.dtype
-    fused = qkv_parts is not None
-    if fused:
-        assert n_parts >= 1 and cos is not None and sin is not None and qkv_parts.dtype == torch.float32 and dt != torch.float32
-        assert cos.dtype == dt and cos.shape[1] == d and cos.is_contiguous() and sin.is_contiguous() and sin.shape == cos.shape
-        assert positions is None or (positions.dtype == torch.int32 and positions.numel() >= T)
-        row_w = (H + 2 * Hkv) * d
-        part_stride = qkv_parts.stride(0) if qkv_parts.dim() == 3 else T * row_w
-        assert qkv_parts.numel() >= (n_parts - 1) * part_stride + T * row_w
-        _check_rope_halves(cos, sin)
-        if sync_flags is not None:
-            assert q is not None and q.dtype == dt and q.stride(-1) == 1 and sync_flags.dtype == torch.int32 and sync_flags.numel() >= Hkv
-    else:
-        _dev(q, "q")
-        assert q.stride(-1) == 1 and q.dtype == dt and sync_flags is None
+    assert q.stride(-1) == 1 and q.dtype == dt
     dev = k_cache.device
     if out is None:
         out = torch.empty(T, H * d, dtype=dt, device=dev)
@@ -145,12 +106,8 @@ def attn_fwd(q: Optional[torch.Tensor], k_cache: torch.Tensor, vt_cache: torch.T
         if part_ml is None:
             part_ml = torch.empty(n_splits, H, T, 2, dtype=torch.float32, device=dev)
     a = AttnArgs(ptr(q), ptr(k_cache), ptr(vt_cache), ptr(out), ptr(part_o), ptr(part_ml), ptr(dyn_P),
-                 (q_row_stride if q_row_stride is not None else q.stride(0)) if q is not None else 0, out.stride(0), H, Hkv, d, S_max,
+                 q_row_stride if q_row_stride is not None else q.stride(0), out.stride(0), H, Hkv, d, S_max,
                  DTYPE_CODE_OF(dt), n_splits, scale if scale is not None else 1.0 / math.sqrt(d), mask.c_struct(), int(wg_rows))
-    if fused:
-        a.n_parts, a.qkv_parts, a.part_stride = int(n_parts), ptr(qkv_parts), int(part_stride)
-        a.positions, a.cos_tab, a.sin_tab, a.max_pos = ptr(positions), ptr(cos), ptr(sin), int(cos.shape[0])
-        a.sync_flags = ptr(sync_flags)
     call("lade_attn_fwd", C.byref(a))
     if n_splits > 1:
         call("lade_attn_combine", C.byref(a))
@@ -472,20 +429,6 @@ def gemm_parts(a: torch.Tensor, w: torch.Tensor, part: torch.Tensor, n_split: in
     if n_split * M * N > part.numel():
         raise cabi.LadeHipError(f"split-K workspace too small: {n_split} x {M} x {N} fp32 partials > {part.numel()}")
     _gemm(a, w, None, 0, ptr(part), n_split, bn, mb, mt, nt, 0, ring)
-
-
-RA_KT = 20          # K tiles a work-group of the register-resident-activation GEMM holds (gemm_decl.hpp)
-
-
-def gemm_ra_parts(a: torch.Tensor, w_kt: torch.Tensor, part: torch.Tensor, n_split: int, cs: int = 4, n_groups: int = 0) -> None:
-    """split-K GEMM with register-resident activations (M <= 128 rows, K-tile-major weight): n_split fp32 partials in `part`, bit-identical
-    to gemm_parts with the same n_split."""
-    M, K = a.shape
-    assert a.stride(1) == 1 and w_kt.dim() == 3 and w_kt.is_contiguous() and w_kt.shape[0] * 64 == K and w_kt.shape[2] == 64
-    N = w_kt.shape[1]
-    if n_split * M * N > part.numel():
-        raise cabi.LadeHipError(f"split-K workspace too small: {n_split} x {M} x {N} fp32 partials > {part.numel()}")
-    call("lade_gemm_ra_kt", ptr(a), a.stride(0), ptr(w_kt), ptr(part), M, N, K, n_split, cs, n_groups, dtype_code(a))
 
 
 def add_rmsnorm_parts(x: torch.Tensor, part: torch.Tensor, n_parts: int, w: torch.Tensor, eps: float, out: torch.Tensor) -> torch.Tensor:

@@ -83,7 +83,7 @@ class KernelDecisions:
     """mixin of StepEngine: kernel decisions per (projection | attention launch, row class)"""
 
     def attn_choice(self, T: int):
-        """(fused RoPE, work-group rows, split mode) of the attention launch of a T-row step.  Decided once per row class - inside a step
+        """(0, work-group rows, split mode) of the attention launch of a T-row step.  Decided once per row class - inside a step
         where the engine can probe one (_refine_in_step) - so that eager steps, hipGraph steps and lookahead-parallel replicas all launch
         the same kernels (16-bit partials round alike)."""
         if self.dtype == torch.float32:
@@ -159,6 +159,8 @@ class KernelDecisions:
                     v = row[n]
                     self.gemm_cfg[(n, m)] = None if v is None else tuple(int(x) for x in v)
             if "attn" in row:
+                if int(row["attn"][0]) != 0:        # the slot of the fused RoPE + KV append forms (removed: DESIGN 4.9)
+                    raise cabi.LadeHipError(f"LADE_TUNE_FILE={path}: row class {m} selects a fused-RoPE attention form ({row['attn'][:3]}), which this library no longer has")
                 self.attn_cfg[m] = tuple(int(x) for x in row["attn"][:3])
             if all(n in row for n in self.LAYER_GEMMS):
                 self._refined.add(m)
@@ -411,7 +413,7 @@ class KernelDecisions:
         attention pair, RoPE and both norms in place, the consumers reading the partials), one graph per candidate - the short list x
         ring depths, plus the best candidate of each smaller split count - replayed round-robin; projection after projection
         (coordinate descent, one pass), a challenger replaces the incumbent only when it wins by > 0.3 %.  Round 5: the ATTENTION launch
-        is the fifth coordinate - (RoPE + KV append fused into it or not) x (work-group rows 128 / 64 / 32) x (split rule), the launch
+        is the fifth coordinate - (work-group rows 128 / 64 / 32) x (split rule), the launch
         parameters of lade_attn_args - decided the same way on the same graphs.
         The probe step runs at a FIXED context (STEP_TUNE_CONTEXT keys, or the whole cache of a smaller engine - part of the cache key) on
         cache rows that are saved and restored, and on no live workspace; workspaces too small for the class's probe rows are grown first.
@@ -507,23 +509,18 @@ class KernelDecisions:
         return out[:18]
 
     def _attn_candidates(self, mclass: int, T: int, S_tot: int):
-        """(fused, work-group rows, split mode) x what they resolve to at the probe context, one entry per distinct launch.
+        """(0, work-group rows, split mode) x what they resolve to at the probe context, one entry per distinct launch.
         Round 6: the attention launch is FROZEN at the default (two launches, 128-row work-groups, sqrt split rule) - round 5's in-step
         pass found every candidate within 0.2-1.5 % of it at every BASELINE shape (profiles/r5_attn_tune.txt: inside the bench's own block
         noise), while a box-dependent choice of the split count made the 16-bit token stream and the PMC evidence box-dependent.
-        LADE_DEBUG=attn_tune brings the coordinate back (experiments); the fused-RoPE forms are candidates only in a -DLADE_EXPERIMENTAL build."""
+        LADE_DEBUG=attn_tune brings the coordinate back (experiments)."""
         inc = self.attn_cfg.get(mclass, self.attn_default)
         if cabi.debug("attn_tune", "0") != "1":
             return [inc]
-        qkv = self.gemm_cfg.get(("wqkv", mclass))
-        fused_ok = (cabi.experimental() and not self.has_epilogue and qkv is not None and qkv[3] >= 0 and qkv[2] <= 4 and cabi.debug("fuse_rope", "") not in ("", "off"))
-        fuses = (1, 0) if fused_ok else (0,)          # (the producer mode, fused = 2, only ever by LADE_DEBUG=fuse_rope=2 as the default: never picked by a tuner)
         rows = (self.H // self.Hkv) * T
         shapes = [128, 64] + ([32] if rows <= 64 or self.H != self.Hkv else [])
         out, seen = [], set()
-        for cand in [inc] + [(f, wg, mode) for f in fuses for wg in shapes for mode in (0, 1, 2)]:
-            if cand[0] and not fuses[0]:
-                continue
+        for cand in [inc] + [(0, wg, mode) for wg in shapes for mode in (0, 1, 2)]:
             key = (cand[0], cand[1], self.n_splits_for(T, S_tot, choice=cand))
             if key not in seen:
                 seen.add(key)
@@ -594,7 +591,7 @@ class KernelDecisions:
                     top = " ".join(f"{c}:{t * 1e3:.1f}" for c, t in sorted(times.items(), key=lambda kv: kv[1])[:6])
                     print(f"[tune-step] {name}:{mclass} rows={T} isolated choice {inc} {times.get(inc, float('nan')) * 1e3:.1f} us/layer -> {pick} "
                           f"{times[pick] * 1e3:.1f} | {top}", file=sys.stderr, flush=True)
-            # the attention launch: fused RoPE + KV append or not, work-group rows, split rule
+            # the attention launch: work-group rows, split rule
             inc = self.attn_cfg[mclass]
 
             def apply_attn(cand):
@@ -611,7 +608,7 @@ class KernelDecisions:
                                "ms_per_layer_in_step_choice": round(times[pick], 5), "candidates": len(times), "probe_context": ctx,
                                "n_splits_at_probe": self.n_splits_for(T, P + T, choice=pick),
                                "ranked_us_per_layer": [[list(c), round(t * 1e3, 2)] for c, t in sorted(times.items(), key=lambda kv: kv[1])[:8]],
-                               "fields": "(RoPE + KV append fused into the launch, work-group rows, split mode 0 sqrt | 1 fill | 2 half)"}
+                               "fields": "(0, work-group rows, split mode 0 sqrt | 1 fill | 2 half)"}
                 if cabi.debug("tune_verbose"):
                     top = " ".join(f"{c}:{t * 1e3:.1f}" for c, t in sorted(times.items(), key=lambda kv: kv[1])[:8])
                     print(f"[tune-step] attn:{mclass} rows={T} default {inc} {times.get(inc, float('nan')) * 1e3:.1f} us/layer -> {pick} {times[pick] * 1e3:.1f} | {top}",
@@ -642,7 +639,7 @@ class KernelDecisions:
 
     def tune_all(self) -> dict:
         """Every (projection, row class) decision of this engine - and the attention launch parameters per row class (`attn:<class>` =
-        (fused RoPE, work-group rows, split mode, 0, 0, 0)) - as a plain dict (lookahead parallelism: rank 0 tunes, the other ranks adopt
+        (0, work-group rows, split mode, 0, 0, 0)) - as a plain dict (lookahead parallelism: rank 0 tunes, the other ranks adopt
         its table through `adopt_gemm_cfg`, so that all replicas round alike)."""
         if not self.custom_gemm:
             return {}

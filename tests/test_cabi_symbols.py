@@ -32,7 +32,18 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
         assert hasattr(lib, s), f"{s} declared in lade_hip.h but not exported"
         assert s in cabi.SIGNATURES, f"{s} has no ctypes signature"
     assert sorted(cabi.SIGNATURES) == syms
-    assert lib.lade_version() == cabi.ABI_VERSION == 3
+    assert lib.lade_version() == cabi.ABI_VERSION == 4
+
+
+def test_attn_args_has_the_size_the_library_was_compiled_with():
+    """csrc/attn.hip pins sizeof(lade_attn_args) with a static_assert on the same number: 7 pointers, 2 x int64, 6 x int32, float, the 9 x int32 mask
+    and wg_rows, padded to 8 bytes.  A field added or dropped on one side only fails here or at compile time."""
+    from lookaheaddecoding_amd import cabi
+    src = open(os.path.join(ROOT, "lookaheaddecoding_amd", "csrc", "attn.hip")).read()
+    pinned = re.findall(r"static_assert\(sizeof\(lade_attn_args\) == (\d+),", src)
+    assert pinned == ["144"]
+    assert C.sizeof(cabi.AttnArgs) == 144
+    assert cabi.AttnArgs._fields_[-1][0] == "wg_rows"
 
 
 def test_argument_validation_returns_error_codes_not_crashes(lib):
@@ -44,6 +55,22 @@ def test_argument_validation_returns_error_codes_not_crashes(lib):
     assert rc == -1
     rc = lib.lade_pool_lookup(None, None, 10, 0, 3, None, None, None, None)
     assert rc == -1 and b"lade_pool_lookup" in lib.lade_last_error_string()
+
+
+def test_a_failure_inside_a_gemm_launch_keeps_its_own_code_and_message(lib):
+    """the shape (160 rows x 256 weight rows, one wave holding five m-blocks) IS in the table, but 8 stages x 52 KB exceed the LDS: launch_gemm's
+    own message must reach the caller instead of being retried in the other groups of the table and overwritten by "no kernel for ..."
+    (the check runs before any launch: dummy non-null pointers, no GPU)"""
+    buf = (C.c_char * 64)()
+    p = C.addressof(buf)
+    M, N, K = 160, 256, 64
+    rc = lib.lade_gemm_skinny(p, K, p, K, p, N, None, M, N, K, 1, 256, 5, 5, 1, 8, 0, 0, None)
+    msg = lib.lade_last_error_string()
+    assert rc == -1, (rc, msg)                     # LADE_E_ARG
+    assert b"does not fit" in msg and b"no kernel for" not in msg, msg
+    # ... and a wave grid that no group of the table holds still says so
+    rc = lib.lade_gemm_skinny(p, K, p, K, p, N, None, M, N, K, 1, 256, 5, 5, 4, 0, 0, 0, None)
+    assert rc == -1 and b"no kernel for" in lib.lade_last_error_string()
 
 
 def test_missing_library_fails_loudly(tmp_path):

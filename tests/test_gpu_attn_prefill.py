@@ -212,10 +212,8 @@ def test_prefill_attention_argument_validation():
     assert lib.lade_attn_prefill(C.byref(a), None) == 0            # the valid form of the same arguments is accepted
     torch.cuda.synchronize()
     dynp = torch.zeros(1, dtype=torch.int32, device="cuda")
-    parts = torch.zeros(16, dtype=torch.float32, device="cuda")
     for what, (a, keep), word in (("is_prefill = 0", args(is_prefill=False), b"is_prefill"),
                                   ("fp32", args(dtype=torch.float32), b"dtype"),
-                                  ("n_parts > 0", args(n_parts=2, qkv_parts=parts.data_ptr()), b"n_parts"),
                                   ("dyn_P", args(dyn_P=dynp.data_ptr()), b"dyn_P"),
                                   ("d = 96", args(d=96), b"head_dim")):
         rc = lib.lade_attn_prefill(C.byref(a), None)

@@ -747,3 +747,28 @@ def test_rmsnorm_every_block_shape_vs_torch():
                 ops.add_rmsnorm_parts(xd, part, n_parts, w.cuda(), 1e-5, y3)
                 assert torch.equal(xd.cpu(), xs), (dtype, hidden, n_parts)
                 assert torch.allclose(y3.cpu().float(), ref_norm(xs).float(), **tol), (dtype, hidden, n_parts)
+
+
+def test_work_group_shape_is_a_launch_parameter_with_equal_results_up_to_rounding():
+    """wg_rows 128 / 64 / 32: same attention within the attention tolerance (the shapes merge their key parts in different orders), each
+    against the dense fp32 oracle"""
+    from lookaheaddecoding_amd import ops
+    torch.manual_seed(9)
+    H, Hkv, d, P = 8, 2, 128, 777
+    ls, lguess, gs = [14, 15, 15, 15], 20, 4
+    T = 1 + sum(ls) + lguess
+    S = P + T
+    lay = O.StepLayout(ids=[0] * T, positions=[], n_input=1, level_sizes=ls, lguess=lguess, is_prefill=False, window=15)
+    vis = O.dense_mask(lay, P, gs)
+    q = torch.randn(T, H, d).bfloat16()
+    k = torch.randn(Hkv, S + 64, d).bfloat16()
+    v = torch.randn(Hkv, S + 64, d).bfloat16()
+    ref = O.attention_dense(q.float().transpose(0, 1), k.float()[:, :S], v.float()[:, :S], vis).transpose(0, 1).reshape(T, H * d)
+    S_max = (S + 127) // 64 * 64
+    kc = torch.zeros(Hkv, S_max, d, dtype=torch.bfloat16); kc[:, :S + 64] = k
+    vt = torch.zeros(Hkv, d, S_max, dtype=torch.bfloat16); vt[:, :, :S + 64] = v.transpose(1, 2)
+    m = ops.StepMask.from_levels(1, ls, lguess, gs, P)
+    for wg in (0, 128, 64, 32):
+        for ns in (1, 2, 5):
+            out = ops.attn_fwd(q.reshape(T, H * d).cuda(), kc.cuda(), vt.cuda(), m, H=H, Hkv=Hkv, d=d, n_splits=ns, wg_rows=wg).float().cpu()
+            assert torch.allclose(out, ref, atol=2e-2, rtol=2e-2), (wg, ns, (out - ref).abs().max().item())

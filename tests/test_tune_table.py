@@ -43,3 +43,35 @@ def test_shipped_table_is_for_this_library_and_names_built_kernels():
                     assert (mb // mt, mt, bn // 32 // nt, nt) in shapes, (name, m, c)
                 n += 1
     assert n >= 60
+
+
+def test_a_row_that_selects_a_fused_rope_attention_form_is_refused(tmp_path):
+    """the attention triple keeps its leading slot (0 in every table written since round 6) so that old and new tables read alike; a row that
+    asks for one of the removed fused RoPE + KV append forms there is an error, not a silently different launch"""
+    import pytest
+    from lookaheaddecoding_amd.tuning import KernelDecisions
+
+    class Stub(KernelDecisions):
+        ROW_CLASSES, GEMM_NAMES, LAYER_GEMMS = StepEngine.ROW_CLASSES, StepEngine.GEMM_NAMES, StepEngine.LAYER_GEMMS
+
+        def __init__(self):
+            self.gemm_cfg, self.attn_cfg, self._refined, self.tune_loaded, self.tune_source = {}, {}, set(), [], None
+
+        def _tune_header(self):
+            return {"version": 1}
+
+        def _tune_key(self):
+            return "model"
+
+    m = str(StepEngine.ROW_CLASSES[0])
+    for first, ok in ((0, True), (1, False), (2, False)):
+        path = tmp_path / f"t{first}.json"
+        path.write_text(json.dumps({"header": {"version": 1}, "models": {"model": {m: {"attn": [first, 128, 0]}}}}))
+        eng = Stub()
+        if ok:
+            eng._load_tune_file(str(path))
+            assert eng.attn_cfg == {int(m): (0, 128, 0)}
+        else:
+            with pytest.raises(cabi.LadeHipError, match="fused-RoPE"):
+                eng._load_tune_file(str(path))
+            assert eng.attn_cfg == {}

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Builds a variant of liblade_hip.so for A/B experiments on the GPU box: tools/build_variant.sh NAME "EXTRA HIPCC FLAGS" [EXPERIMENTAL=1]
+# Builds a variant of liblade_hip.so for A/B experiments on the GPU box: tools/build_variant.sh NAME "EXTRA HIPCC FLAGS" [MAKE VARIABLES ...]
 # -> lookaheaddecoding_amd/liblade_hip_NAME.so (select it with LADE_HIP_LIB=<path>); objects under csrc/build_NAME/.
 set -e
 cd "$(dirname "$0")/../lookaheaddecoding_amd/csrc"

@@ -1,7 +1,7 @@
 """What clock and power the chip sustains under the weight-streaming GEMM at different row classes ("the MFMA phase costs
 clock" - is the 128-row class running into the power budget?).  A hipGraph of 40 gate/up launches (13B width, rotating weights) is replayed for
 SECONDS per case while a thread samples `amd-smi metric --clock --power` (falls back to `rocm-smi`); prints us per launch, the sampled
-socket power and GFX clock per case.  Cases: M rows x {random, all-zero operands} x {ring kernel, RA kernel}."""
+socket power and GFX clock per case.  Cases: M rows x {random, all-zero operands}."""
 import json
 import os
 import subprocess
@@ -34,15 +34,12 @@ def raw_once():
 
 kts = [ops.to_ktile((torch.randn(N, K, device="cuda") * 0.02).to(DT)) for _ in range(4)]
 kz = [torch.zeros_like(k) for k in kts[:2]]
-part = torch.empty(4 * 128 * N, dtype=torch.float32, device="cuda")
 print("idle:", sample(), flush=True)
-CASES = ((60, False, "ring"), (120, False, "ring"), (120, True, "ring"), (60, False, "ra"), (120, False, "ra"), (120, True, "ra"), (1, False, "ring"))
+CASES = ((60, False), (120, False), (120, True), (1, False))
 if os.environ.get("CASES"):            # CASES=76,100,120: random operands on the ring kernel at these row counts (LADE_DEBUG=gemm_dbg=256: zero padding rows)
-    CASES = tuple((int(m), False, "ring") for m in os.environ["CASES"].split(","))
+    CASES = tuple((int(m), False) for m in os.environ["CASES"].split(","))
     print("LADE_DEBUG =", os.environ.get("LADE_DEBUG", ""))
-for M, zero, kind in CASES:
-    if kind == "ra" and not __import__("lookaheaddecoding_amd.cabi", fromlist=["x"]).experimental():
-        continue                      # the RA kernel lives in the EXPERIMENTAL build only
+for M, zero in CASES:
     a = torch.zeros(M, K, device="cuda", dtype=DT) if zero else torch.randn(M, K, device="cuda").to(DT)
     ws = kz if zero else kts
     act = torch.empty(M, N // 2, dtype=DT, device="cuda")
@@ -51,10 +48,7 @@ for M, zero, kind in CASES:
 
     def run():
         i[0] = (i[0] + 1) % len(ws)
-        if kind == "ring":
-            ops.gemm_swiglu(a, ws[i[0]], act, 128 if mb == 4 else 96, mb, 2 if mb == 4 else (mb if mb in (3, 5) else 1), 1, 3 if mb == 4 else (8 if mb < 3 else 0))
-        else:
-            ops.gemm_ra_parts(a, ws[i[0]], part, 4, 4)
+        ops.gemm_swiglu(a, ws[i[0]], act, 128 if mb == 4 else 96, mb, 2 if mb == 4 else (mb if mb in (3, 5) else 1), 1, 3 if mb == 4 else (8 if mb < 3 else 0))
     for _ in range(3):
         run()
     torch.cuda.synchronize()
@@ -89,7 +83,7 @@ for M, zero, kind in CASES:
     pw = sum(s[0] for s in good) / len(good) if good else float("nan")
     ck = [s[1] for s in samples if s and isinstance(s[1], float)]
     ckm = [s[2] for s in samples if s and isinstance(s[2], float)]
-    print(f"gate/up 13B M={M:3d} {'zero  ' if zero else 'random'} {kind:4s}: {us:7.2f} us per launch ({N * K * 2 / 1e6 / us:4.2f} TB/s)  power {pw:6.1f} W  gfx clock mean {sum(ck) / len(ck) if ck else float('nan'):7.1f} "
+    print(f"gate/up 13B M={M:3d} {'zero  ' if zero else 'random'}: {us:7.2f} us per launch ({N * K * 2 / 1e6 / us:4.2f} TB/s)  power {pw:6.1f} W  gfx clock mean {sum(ck) / len(ck) if ck else float('nan'):7.1f} "
           f"max {max(ckm) if ckm else float('nan'):7.1f} MHz  ({len(samples)} samples{'' if good else '; first: ' + str(samples[:1])})", flush=True)
 if not os.environ.get("CASES"):
     raw_once()

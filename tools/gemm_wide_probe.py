@@ -16,8 +16,6 @@ HID, INTER, QKV = {"7b": (4096, 11008, 12288), "13b": (5120, 13824, 15360), "70b
 DT = torch.float16 if os.environ.get("PROBE_DTYPE") == "f16" else torch.bfloat16
 # (bn, mb, mt, nt): wave grids built for 256-row blocks (gemm_kernel.hpp)
 CANDS = [(128, 8, 4, 1, 0), (128, 8, 4, 2, 0), (128, 8, 2, 2, 0), (64, 8, 4, 1, 0), (256, 8, 4, 2, 0), (256, 8, 2, 4, 0)]
-if cabi.experimental():          # the ping-pong K loop (csrc/gemm_pp.hpp, ring = 10 + stages) at its 256-row shapes: the compute-bound regime it was NOT measured in
-    CANDS += [(128, 8, 4, 2, 10), (128, 8, 4, 2, 12), (128, 8, 4, 2, 14), (64, 8, 4, 1, 10), (64, 8, 4, 1, 14), (64, 8, 4, 1, 16)]
 
 
 def timeit(fn, reps=12, rounds=3):
