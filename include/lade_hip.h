@@ -53,6 +53,8 @@
  *                            Llama only
  *   lade_gen_ctl_init / lade_gen_ctl_update / lade_gen_argmax / lade_gen_rows / lade_greedy_post_step_ex   HF's repetition penalty,
  *                            min-length processors and EOS sets on the step's rows (the reference refuses them, lade/decoding.py:968)
+ *   lade_emit_init / lade_emit_rows   the `scores` / `logits` tuples of generate(return_dict_in_generate=True): the reference refuses them
+ *                            (lade/decoding.py:967 greedy, the matching assertion at the head of jacobi_sample_multilevel's loop for sampling)
  *   lade_time_attn / lade_time_attn_rot   hipEvent timing helpers for bench.py (no reference counterpart)
  */
 #ifndef LADE_HIP_H
@@ -68,7 +70,8 @@ extern "C" {
                                  * 3: + lade_gemm_ra_kt, lade_build_flags; + lade_gen_ctl_init, lade_gen_ctl_update, lade_gen_argmax,
                                  *    lade_gen_rows, lade_greedy_post_step_ex (nothing that existed changed);
                                  * 4: the measured-and-dropped kernels are gone: lade_attn_args ends at wg_rows (n_parts, qkv_parts, part_stride, positions,
-                                 *    cos_tab, sin_tab, max_pos, sync_flags removed), lade_gemm_ra_kt and lade_build_flags removed; nothing else changed */
+                                 *    cos_tab, sin_tab, max_pos, sync_flags removed), lade_gemm_ra_kt and lade_build_flags removed; nothing else changed
+                                 *    (+ lade_emit_init, lade_emit_rows since: nothing that existed changed, the number stays) */
 
 /* error codes */
 #define LADE_OK 0
@@ -345,6 +348,38 @@ int lade_gen_argmax(const void* logits, int64_t ld, int32_t rows, int32_t V, int
 int lade_gen_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t dtype, int32_t n_inp, int32_t gs,
                   const int32_t* gen, const int32_t* ctl, const int32_t* guess, const int32_t* pos, const int32_t* sel,
                   int32_t* am, float* rows_out, void* stream);
+
+/* ---- emitted rows (generate(return_dict_in_generate=True, output_scores / output_logits); additive to ABI 4) --------------------------
+ * HF returns, per generated token, the fp32 row that decided it: `logits` = the model's row (`.to(float32)`), `scores` = that row after
+ * the logits processors / warpers.  A lookahead step emits 1 .. gs + 1 tokens; which rows decided them:
+ *   token 0 of a step      the out row:                       raw row 0,                         processed row 0
+ *   token k >= 1           position k-1 of the accepted candidate c:  raw row 1 + n_inp + c*gs + (k-1),   processed row 1 + c*gs + (k-1)
+ * (raw = the step's materialised logits [out | n_inp window rows | candidate rows], model dtype; processed = the rows_out layout of
+ * lade_gen_rows / lade_warp_rows, fp32, no window rows).
+ * The destinations live in a device descriptor of LADE_EMIT_WORDS int64 words, never in kernel arguments, so a captured step appends to
+ * whatever buffers the descriptor names at replay:
+ *   desc[LADE_EMIT_SCORES], desc[LADE_EMIT_LOGITS]   destination buffers, fp32 [cap_rows][ld] (either may be null: not written)
+ *   desc[LADE_EMIT_CAP]    rows the buffers hold        desc[LADE_EMIT_LD]   their row stride in elements (= V)
+ *   desc[LADE_EMIT_COUNT]  rows appended so far; it keeps counting beyond cap_rows (rows at or beyond the capacity are not written), so the
+ *                          host detects an overflow by reading it */
+#define LADE_EMIT_SCORES 0
+#define LADE_EMIT_LOGITS 1
+#define LADE_EMIT_CAP 2
+#define LADE_EMIT_LD 3
+#define LADE_EMIT_COUNT 4
+#define LADE_EMIT_WORDS 8
+/* Writes the descriptor (counter = 0): once per generate() call, in place - no re-capture.  At least one destination must be non-null. */
+int lade_emit_init(int64_t* desc, float* scores_buf, float* logits_buf, int64_t cap_rows, int32_t V, void* stream);
+/* Appends the rows of the tokens one step emitted, in emission order, at desc[LADE_EMIT_COUNT], then advances the counter (a one-thread
+ * launch behind the row kernel).  raw [..][raw_ld] in raw_dtype, widened to fp32 (exact).  proc (nullable) fp32 [..][proc_ld]: the source of
+ * `scores`; null = scores are the widened raw rows (greedy without controls: HF's scores and logits hold the same values).
+ * Which rows: idx == NULL (greedy, also inside a captured step, behind the post-step): n = ctl[LADE_CTL_N_ACCEPT] tokens of candidate
+ * ctl[LADE_CTL_MAX_HIT_IDX], read on the device.  Otherwise idx is a HOST array copied into the launch: n_idx (1 .. gs + 1) tokens, token
+ * k >= 1 from candidate idx[k] (idx[0] is not read) - the sampling path, whose verify runs on the host.
+ * Grid (gs + 1 token slots) x (column blocks); a slot at or above n exits at once.  16-byte loads and stores where V, the strides and the
+ * pointers allow them, a scalar tail otherwise; plain stores only. */
+int lade_emit_rows(int64_t* desc, const void* raw, int64_t raw_ld, int32_t raw_dtype, int32_t n_inp, int32_t gs, const float* proc,
+                   int64_t proc_ld, const int32_t* ctl, const int32_t* idx, int32_t n_idx, int32_t V, void* stream);
 
 /* lookahead parallelism: record packing, then (after the all-gather of rec_words int32 per rank, lade_lp_allgather
  * or the host's collective) the deterministic reduction every rank applies (same phases as above).

@@ -29,6 +29,8 @@ MAX_LEVEL, MAX_WINDOW, MAX_GUESS_SET = 16, 128, 64
 REC_WORDS = 8 + MAX_LEVEL
 # generation-control block (include/lade_hip.h: LADE_GEN_*)
 GEN_MAX_EOS, GEN_SEEN, GEN_MAX_VOCAB = 8, 16, 1 << 18
+# emitted-rows descriptor (include/lade_hip.h: LADE_EMIT_*), int64 words
+EMIT_SCORES, EMIT_LOGITS, EMIT_CAP, EMIT_LD, EMIT_COUNT, EMIT_WORDS = 0, 1, 2, 3, 4, 8
 
 
 def gen_words(V: int) -> int:
@@ -98,6 +100,8 @@ SIGNATURES = {
     "lade_gen_ctl_update": [_vp, _vp, _vp],
     "lade_gen_argmax": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lade_gen_rows": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lade_emit_init": [_vp, _vp, _vp, _i64, _i32, _vp],
+    "lade_emit_rows": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _vp],
     "lade_lp_pack": [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp],
     "lade_lp_reduce_apply": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp],
     "lade_lp_unique_id": [_vp],

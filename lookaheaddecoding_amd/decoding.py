@@ -68,6 +68,30 @@ class GenOut:
     steps: int
     generated: int
     trace: List[dict] = field(default_factory=list)
+    scores: Optional[torch.Tensor] = None      # emit request only: [generated, V] fp32 device rows, HF's `scores` (processed / warped)
+    logits: Optional[torch.Tensor] = None      # ... and HF's `logits` (the model's rows, widened to fp32)
+
+
+EMIT_FIELDS = ("scores", "logits")
+LP_EMIT_REFUSAL = ("lookahead parallelism (DIST_WORKERS > 1 / FORCE_LP) does not implement return_dict_in_generate with output_scores / "
+                   "output_logits: its verify runs inside lade_lp_reduce_apply, which keeps no rows; run on one GPU without FORCE_LP")
+
+
+def emit_request(emit) -> Optional[tuple]:
+    """An emit request in canonical form: None (off), or the requested subset of EMIT_FIELDS in that order"""
+    if not emit:
+        return None
+    if isinstance(emit, str):
+        emit = (emit,)
+    unknown = [f for f in emit if f not in EMIT_FIELDS]
+    if unknown:
+        raise cabi.LadeHipError(f"emit={tuple(emit)!r}: unknown field {unknown[0]!r} (one or both of {EMIT_FIELDS})")
+    return tuple(f for f in EMIT_FIELDS if f in emit) or None
+
+
+def emit_capacity(max_length: int, n_prompt: int, gs: int) -> int:
+    """rows of a run's emit buffers: every token up to max_length, plus what the last step may emit beyond it"""
+    return max(int(max_length) - int(n_prompt), 0) + int(gs)
 
 
 # ---- the shape of one decode step: plain host arithmetic, shared by the single-GPU decoder and lookahead parallelism -------------
@@ -253,9 +277,12 @@ class LookaheadDecoder:
         self._gen = None                  # generation-control block (start)
         self._smp = None                  # pinned and device sampling buffers (_sampling_buffers)
         self._draw_warm = False           # the device draw's torch kernels have run once (sample_start)
+        # per-token scores / logits (start(emit=...)): the request, the run's buffers, the device descriptor the captured steps read
+        # (allocated once: its ADDRESS is baked into the graphs, its contents are rewritten per run), the rows of the last model step
+        self.emit, self._emit_bufs, self._emit_desc, self._emit_src = None, {}, None, None
         self._sel_cache = {}              # device copies of the eager steps' logits-row selections (_set_sel)
         # captured steady steps, per candidate bucket (_capture_graphs); _graph_key: what they were captured for (_graph_key_for)
-        self._graphs, self._graph_sel, self._graph_splits, self._graph_T, self._graph_logits = {}, {}, {}, {}, {}
+        self._graphs, self._graph_sel, self._graph_splits, self._graph_T, self._graph_logits, self._graph_src = {}, {}, {}, {}, {}, {}
         self._graph_key = None
         # every kernel decision the steady steps of this configuration need (GEMM shapes, the in-step pass, the attention launch
         # parameters) is taken NOW, not inside the first live step of each row class (a multi-second stall for that request)
@@ -283,9 +310,11 @@ class LookaheadDecoder:
     @torch.no_grad()
     @_on_device
     def start(self, prompt: Sequence[int], eos_token_id=None, rng: Optional[random.Random] = None,
-              controls: Optional[GenControls] = None) -> None:
-        """eos_token_id: an int, a sequence of ints or None.  controls: GenControls (repetition penalty / min length) or None; with None
-        and at most one EOS id a step launches exactly the kernels of the plain step."""
+              controls: Optional[GenControls] = None, emit=None, emit_cap: int = 0) -> None:
+        """eos_token_id: an int, a sequence of ints or None.  controls: GenControls (repetition penalty / min length) or None; with None,
+        at most one EOS id and no emit request a step launches exactly the kernels of the plain step.
+        emit: None, or one or both of "scores" / "logits": every step appends the fp32 rows that decided its tokens to per-run buffers of
+        emit_cap rows (emit_capacity); emitted() returns them."""
         e, st = self.e, self.st
         W, N, G, gs = self.W, self.N, self.G, self.gs
         rng = rng if rng is not None else random
@@ -307,10 +336,38 @@ class LookaheadDecoder:
             mask_eos = self.eos_set if c.min_len_eos is None else eos_set(c.min_len_eos)
             ops.gen_ctl_init(self._gen, st.V, c.penalty, c.min_len if mask_eos else 0, mask_eos,
                              torch.tensor(self.prompt, dtype=torch.int32, device=e.device))
+        self.emit, self._emit_bufs, self._emit_src = emit_request(emit), {}, None
+        if self.emit is not None:
+            if self._emit_desc is None:
+                self._emit_desc = torch.zeros(cabi.EMIT_WORDS, dtype=torch.int64, device=e.device)
+            self._emit_bufs = {f: torch.empty(max(int(emit_cap), 1), st.V, dtype=torch.float32, device=e.device) for f in self.emit}
+            ops.emit_init(self._emit_desc, self._emit_bufs.get("scores"), self._emit_bufs.get("logits"), st.V)
         self.tokens = list(self.prompt)
         self.steps, self.P, self.g, self.fill_level = 0, 0, 0, 0
         self._step_no = 0                  # st.reset zeroed ctl[STEP]
         self.finished_by_eos = False
+
+    def _emit_step(self, n_inp: int, proc: Optional[torch.Tensor], idx=None) -> None:
+        """Appends the rows of the tokens the step has just emitted (lade_emit_rows): behind the post-step, whose ctl words name them
+        (greedy, idx None), or with the host verify's candidate per token (sampling).  proc: the rows `scores` are taken from."""
+        raw = self._emit_src[0]
+        ops.emit_rows(self._emit_desc, raw, n_inp, self.gs, proc=proc if "scores" in self.emit else None, ctl=self.st.ctl, idx=idx)
+
+    def emitted(self, n: int) -> dict:
+        """The first n emitted rows of the run per requested field ([n, V] fp32 views of the run's buffers).  Raises when the steps
+        appended more rows than the buffers hold, or fewer than n."""
+        if self.emit is None:
+            return {}
+        count = int(self._emit_desc[cabi.EMIT_COUNT].item())
+        cap = next(iter(self._emit_bufs.values())).shape[0]
+        if count > cap or count < n:
+            raise cabi.LadeHipError(f"emit buffers: the steps appended {count} rows, the buffers hold {cap}, {n} tokens were returned")
+        return {f: b[:n] for f, b in self._emit_bufs.items()}
+
+    def _with_emitted(self, out: GenOut) -> GenOut:
+        rows = self.emitted(out.generated)
+        out.scores, out.logits = rows.get("scores"), rows.get("logits")
+        return out
 
     def _post_step(self, am, n_inp: int, T: int, cand_rows: int, phase: int, forced=None, level_override=None, record_host=None) -> None:
         """The fused post-step (+ the seen-set update under controls).  At most one EOS id and no controls: lade_greedy_post_step, the
@@ -333,9 +390,12 @@ class LookaheadDecoder:
         no window rows between).  logits None: the lm_head GEMM has taken the argmax already."""
         st = self.st
         if self.controls is not None:
-            rows_out = torch.empty(1 + shape.cand_rows, st.V, dtype=torch.float32, device=self.e.device) if want_rows else None
+            need_rows = want_rows or (self.emit is not None and "scores" in self.emit)      # (emit: the processed rows are HF's `scores`)
+            rows_out = torch.empty(1 + shape.cand_rows, st.V, dtype=torch.float32, device=self.e.device) if need_rows else None
             ops.gen_argmax(logits, shape.n_inp, self.gs, self._gen, st.ctl, st.guess, pos, sel, st.am, rows_out)
-            return rows_out
+            self._emit_src = (logits, rows_out)
+            return rows_out if want_rows else None
+        self._emit_src = (logits, None)
         if logits is None:
             return None
         if want_rows and not captured:                    # (the captured forward-only body converts AFTER the argmax: the order of its launches is kept)
@@ -351,7 +411,8 @@ class LookaheadDecoder:
         and candidate count from the control block.  Lookahead parallelism feeds window columns [c0, c1), its share of the guesses
         and, captured, lp = (rank, world).
         Greedy steps take the row argmax inside the lm_head GEMM (argmax_out: the logits are never materialised); the sampling verify
-        needs the rows themselves, and under generation controls the lm_head materialises them and the processed argmax reads them once."""
+        needs the rows themselves, and under generation controls or an emit request the lm_head materialises them (the argmax reads them
+        once, lade_emit_rows copies the deciding ones)."""
         e, st, gs = self.e, self.st, self.gs
         mask = StepMask.from_levels(shape.n_input, shape.level_sizes, shape.cand_rows, gs, P)
         call("lade_build_inputs", None, None, shape.n_input, ptr(st.window), st.wcap, ptr(st.ctl), len(shape.level_sizes) - 1, c0, c1,
@@ -360,7 +421,8 @@ class LookaheadDecoder:
             sel, n_sel = st.sel, self._set_sel(shape.rows())
         else:
             n_sel = sel.numel()
-        logits = e.forward(st.ids, st.pos, mask, sel, n_sel, argmax_out=None if (want_rows or self.controls is not None) else st.am, **device_len)
+        logits = e.forward(st.ids, st.pos, mask, sel, n_sel, argmax_out=None if (want_rows or self.controls is not None or self.emit is not None) else st.am,
+                           **device_len)
         return self._logits_to_am(logits, shape, st.pos, sel, want_rows, captured=bool(device_len))
 
     def _eager_model(self, want_rows: bool):
@@ -415,21 +477,27 @@ class LookaheadDecoder:
         # LADE_POLL (default on): the post-step stores the sealed record straight into the pinned host buffer and the host polls for it;
         # otherwise a copy node carries it and the host synchronises the stream
         self._post_step(st.am, shape.n_inp, shape.T, shape.cand_rows, 2, record_host=st.record_host if self.poll else None)
+        if self.emit is not None:           # which rows: ctl[N_ACCEPT] / ctl[MAX_HIT_IDX] as the post-step left them - no host round trip
+            self._emit_step(shape.n_inp, self._emit_src[1])
         ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
         if not self.poll:
             st.record_host.copy_(st.record, non_blocking=True)
 
     def _graph_key_for(self, forward_only: bool) -> tuple:
         """What captured graphs depend on: the kind of body, whether it launches the generation controls (their VALUES live in device
-        memory: no re-capture), the engine's generation, and - only for the body that contains the post-step - the EOS set."""
-        return (forward_only, self.controls is not None, self.e.generation, None if forward_only else self.eos_set)
+        memory: no re-capture), the emit request (the lm_head materialises its logits and the body launches lade_emit_rows; the BUFFERS are
+        named by the device descriptor: no re-capture), the engine's generation, and - only for the body that contains the post-step - the
+        EOS set."""
+        return (forward_only, self.controls is not None, self.emit, self.e.generation, None if forward_only else self.eos_set)
 
     def _capture_graphs(self, forward_only: bool = False) -> None:
         e, st = self.e, self.st
-        self._graphs, self._graph_sel, self._graph_splits, self._graph_T, self._graph_logits = {}, {}, {}, {}, {}
+        self._graphs, self._graph_sel, self._graph_splits, self._graph_T, self._graph_logits, self._graph_src = {}, {}, {}, {}, {}, {}
         state = (st.ctl, st.window, st.pool_cnt, st.pool_tok, st.guess, st.tail) + (() if e.ntk_state is None else (e.ntk_state,))
         if self.controls is not None:
             state += (self._gen,)           # the warm-up's post-step adds its tokens to the seen set
+        if self.emit is not None and not forward_only:
+            state += (self._emit_desc,)     # ... and its lade_emit_rows advances the row counter (the rows it wrote are overwritten by the real step)
         for gcap in self._buckets():
             shape = StepShape(2, 1, tuple(level_sizes(self.W, self.N, self.N - 2)), gcap * self.gs)
             T = shape.T
@@ -441,6 +509,7 @@ class LookaheadDecoder:
             self._graph_splits[gcap] = e.n_splits_for(T, min(e.S_max, max(self.P + T, 1024)))
             self._graph_T[gcap] = T
             self._graphs[gcap], self._graph_logits[gcap] = capture_step_graph(lambda: self._graph_body(shape, gcap, forward_only), state)
+            self._graph_src[gcap] = self._emit_src          # the captured step's logits (and processed rows) in the graph's memory pool
         torch.cuda.synchronize()
         st.record_host.zero_()              # the warm-up passes left records of the step number the first replay will produce: never mistake one for it
         self._graph_key = self._graph_key_for(forward_only)
@@ -458,6 +527,7 @@ class LookaheadDecoder:
         if self.P + T > e.S_max:
             raise cabi.LadeHipError(f"KV cache exhausted: P={self.P} + T={T} > S_max={e.S_max}")
         self._graphs[gcap].replay()
+        self._emit_src = self._graph_src[gcap]
         return T, gcap * self.gs, self._graph_logits[gcap]
 
     def _polled_record(self) -> List[int]:
@@ -512,6 +582,8 @@ class LookaheadDecoder:
             shape, T, P_before, _ = self._eager_model(want_rows=False)
             phase, n_input = shape.phase, shape.n_input - (P_before if shape.phase == 0 else 0)      # prefill: out row = last prompt token of the last chunk
             self._post_step(st.am, shape.n_inp, T, shape.cand_rows, phase)
+            if self.emit is not None:
+                self._emit_step(shape.n_inp, self._emit_src[1])
             ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
             rec = st.read_record()
         return dict(T=T, P_before=P_before, n_input=n_input, max_hit=rec[0], max_hit_idx=rec[5], first_guess=rec[6], **self._take_record(rec, phase))
@@ -519,11 +591,15 @@ class LookaheadDecoder:
     @torch.no_grad()
     @_on_device
     def greedy(self, prompt: Sequence[int], max_length: int, eos_token_id=None,
-               rng: Optional[random.Random] = None, keep_trace: bool = False, on_step=None, controls: Optional[GenControls] = None) -> GenOut:
+               rng: Optional[random.Random] = None, keep_trace: bool = False, on_step=None, controls: Optional[GenControls] = None,
+               emit=None) -> GenOut:
         """`jacobi_greedy_search_multilevel` (lade/decoding.py:697-1259), single GPU or lookahead parallel.
         on_step(accepted_tokens): called after every step with the tokens it accepted (chat printing / HF streamers,
-        lade/decoding.py:1179-1200)."""
+        lade/decoding.py:1179-1200).  emit: None, or one or both of "scores" / "logits" - the result then carries the [generated, V] fp32
+        rows HF's generate() returns under return_dict_in_generate (the reference refuses that, lade/decoding.py:967)."""
         if self.lp is not None and (self.lp.R > 1 or self.lp.force):
+            if emit_request(emit) is not None:
+                raise cabi.LadeHipError(LP_EMIT_REFUSAL)
             # the lookahead-parallel verify and EOS scan (lade_lp_reduce_apply) know neither the controls nor an EOS set
             if controls is not None and controls.active:
                 raise cabi.LadeHipError("lookahead parallelism (DIST_WORKERS > 1 / FORCE_LP) does not implement repetition_penalty / "
@@ -534,8 +610,8 @@ class LookaheadDecoder:
                                         "run on one GPU without FORCE_LP")
             from .parallel import greedy_lp
             return greedy_lp(self, prompt, max_length, eos[0] if eos else None, rng, keep_trace, on_step=on_step)
-        self.start(prompt, eos_token_id, rng, controls)
-        return generate_loop(self, self.step, max_length, keep_trace, on_step, log=True)
+        self.start(prompt, eos_token_id, rng, controls, emit, emit_capacity(max_length, len(prompt), self.gs))
+        return self._with_emitted(generate_loop(self, self.step, max_length, keep_trace, on_step, log=True))
 
 
     # ---- sampling ------------------------------------------------------------------------------------
@@ -571,11 +647,11 @@ class LookaheadDecoder:
     @torch.no_grad()
     @_on_device
     def sample_start(self, prompt: Sequence[int], warp=None, eos_token_id=None, rng: Optional[random.Random] = None,
-                     torch_gen: Optional[torch.Generator] = None, controls: Optional[GenControls] = None) -> None:
-        """Begins a sampling run (`sample` = sample_start + sample_step until done; bench.py drives single steps)."""
+                     torch_gen: Optional[torch.Generator] = None, controls: Optional[GenControls] = None, emit=None, emit_cap: int = 0) -> None:
+        """Begins a sampling run (`sample` = sample_start + sample_step until done; bench.py drives single steps).  emit / emit_cap: as in start."""
         e, W = self.e, self.W
         rng = rng if rng is not None else random
-        self.start(prompt, eos_token_id, rng, controls)
+        self.start(prompt, eos_token_id, rng, controls, emit, emit_cap)
         if torch_gen is not None and torch_gen.device.type == "cuda" and not self._draw_warm:
             # the draw's torch kernels (exponential, divide, argmax, and the strike-and-renormalise ops of a rejected draft) load their code
             # objects on first use: 10-26 ms in the middle of the first step that rejects a draft.  One dry run on a throw-away generator -
@@ -593,7 +669,7 @@ class LookaheadDecoder:
     @_on_device
     def sample(self, prompt: Sequence[int], max_length: int, warp=None, eos_token_id=None,
                rng: Optional[random.Random] = None, torch_gen: Optional[torch.Generator] = None, keep_trace: bool = False,
-               on_step=None, controls: Optional[GenControls] = None) -> GenOut:
+               on_step=None, controls: Optional[GenControls] = None, emit=None) -> GenOut:
         """`jacobi_sample_multilevel` (lade/decoding.py:137-692), single GPU (the reference has no LP here).
 
         The model step, input assembly, pool and window stay on the GPU, and so do the probabilities: `lade_softmax_gather`
@@ -601,9 +677,13 @@ class LookaheadDecoder:
         consumes the reference's RNG streams, in the reference's order: `rng.random()` once per verification trial,
         one `torch.multinomial` for the token that ends the step (:484-540), and the `filter_window` draws (:578-580).
         `warp`: a sampling.Warper (temperature / top-k / top-p; temperature alone is applied inside the kernels) or any callable
-        mapping fp32 logits rows [r, V] to warped logits (the HF warpers the reference admits, :375-377)."""
-        self.sample_start(prompt, warp, eos_token_id, rng, torch_gen, controls)
-        return generate_loop(self, lambda: self.sample_step(keep_trace), max_length, keep_trace, on_step, log=True)
+        mapping fp32 logits rows [r, V] to warped logits (the HF warpers the reference admits, :375-377).
+        emit: as in greedy; `scores` are the warped rows (after temperature, top-k and top-p) as the verify read them - the strikes of
+        rejected drafts edit the probabilities of the final draw, never these rows."""
+        if self.lp is not None and (self.lp.R > 1 or self.lp.force) and emit_request(emit) is not None:
+            raise cabi.LadeHipError(LP_EMIT_REFUSAL)
+        self.sample_start(prompt, warp, eos_token_id, rng, torch_gen, controls, emit, emit_capacity(max_length, len(prompt), self.gs))
+        return self._with_emitted(generate_loop(self, lambda: self.sample_step(keep_trace), max_length, keep_trace, on_step, log=True))
 
     @torch.no_grad()
     @_on_device
@@ -680,5 +760,17 @@ class LookaheadDecoder:
         self._post_step(st.am, n_inp, T, cand_rows, phase, forced=forced, level_override=level_override)
         ops.kv_commit(e.kv, 0, 0, 0, ctl=st.ctl)
         info = self._take_record(st.read_record(), phase)
+        if self.emit is not None and info["accepted"]:
+            # the rows of the tokens the record says were emitted (an EOS inside the step drops those behind it): token 0 from the out
+            # row, token k from position k-1 of the winning candidate - every draft it accepted was judged under a row of that prefix
+            proc = None
+            if "scores" in self.emit:
+                if fused_T is None:
+                    proc = src if (src.dtype == torch.float32 and src.stride(-1) == 1) else src.float().contiguous()
+                elif temp != 1.0:          # temperature alone runs inside the probability kernels: materialise logits / T for the record
+                    proc = ops.warp_rows(logits, rows, n_skip, temperature=temp)
+                elif self.controls is not None:
+                    proc = logits          # the processed rows themselves
+            self._emit_step(n_inp, proc, idx=[0] + [max_hit_idx] * (len(info["accepted"]) - 1))
         all_old_tokens += info["accepted"]
         return dict(T=T, P_before=P_before, max_hit=max_hit, max_hit_idx=max_hit_idx, **info, **step_inputs)

@@ -21,7 +21,7 @@ from typing import Optional
 import torch
 
 from . import cabi
-from .decoding import CONFIG_MAP, FUNC_MAP, GenControls, LookaheadDecoder, eos_set
+from .decoding import CONFIG_MAP, FUNC_MAP, LP_EMIT_REFUSAL, GenControls, LookaheadDecoder, eos_set
 from .engine import StepEngine
 
 _ENGINE_ATTR = "_lade_engine"
@@ -287,13 +287,49 @@ def controls_from_processors(processors):
     return (ctl if ctl.active else None), rest
 
 
-def _run(self, input_ids, do_sample, warp, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls=None):
+def output_request(generation_config=None, return_dict_in_generate=None, output_scores=None, output_logits=None, output_attentions=None,
+                   output_hidden_states=None):
+    """What generate() was asked to return besides the token ids.  Each flag is the keyword when given (transformers 4.36 passes them to
+    greedy_search / sample) and the attribute of generation_config otherwise (the `_sample` path).  None: a plain tensor, as without
+    return_dict_in_generate; else the emit request of the decode loops - a possibly empty tuple out of "scores" / "logits".  Attentions
+    and hidden states are refused: the step engine runs fused kernels over the step's rows and keeps neither."""
+    def flag(value, name):
+        return bool(getattr(generation_config, name, False) if value is None else value)
+
+    if not flag(return_dict_in_generate, "return_dict_in_generate"):
+        return None
+    for value, name in ((output_attentions, "output_attentions"), (output_hidden_states, "output_hidden_states")):
+        if flag(value, name):
+            raise cabi.LadeHipError(f"{name}=True with return_dict_in_generate is not supported under lookahead decoding: the HIP step engine "
+                                    "materialises no per-layer attention weights or hidden states (scores and logits are supported)")
+    return tuple(f for f, on in (("scores", flag(output_scores, "output_scores")), ("logits", flag(output_logits, "output_logits"))) if on)
+
+
+def generate_output(sequences, result, request):
+    """HF's return value of generate(return_dict_in_generate=True) from a decode loop's result: `scores` / `logits` as tuples of [1, V]
+    fp32 views of result.scores / result.logits ([generated, V]), one per generated token; a field that was not requested is None."""
+    from transformers.generation.utils import GenerateDecoderOnlyOutput
+
+    def rows(name):
+        if name not in request:
+            return None
+        t = getattr(result, name)
+        if t is None or t.shape[0] != result.generated:
+            raise cabi.LadeHipError(f"{name}: {None if t is None else t.shape[0]} rows for {result.generated} generated tokens")
+        return tuple(t[i:i + 1] for i in range(t.shape[0]))
+
+    return GenerateDecoderOnlyOutput(sequences=sequences, scores=rows("scores"), logits=rows("logits"), past_key_values=None)
+
+
+def _run(self, input_ids, do_sample, warp, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls=None, request=None):
     W = CONFIG_MAP.get("WINDOW_SIZE", 60)            # reference defaults when config_lade was never called
     G = CONFIG_MAP.get("GUESS_SET_SIZE", 60)         # (lade/decoding.py:854-857)
     N = CONFIG_MAP.get("LEVEL", 8)
     assert CONFIG_MAP.get("ALWAYS_FWD_ONE", 1) == 1  # :873
     assert input_ids.size(0) == 1, " single batch only "      # modeling_llama.py:1448
     R = CONFIG_MAP.get("DIST_WORKERS", 1)
+    if request is not None and (R > 1 or CONFIG_MAP.get("FORCE_LP", 0)):
+        raise cabi.LadeHipError(LP_EMIT_REFUSAL)
     max_length, eos_c = _criteria_limits(stopping_criteria, generation_config)
     eos_token_id = eos_set(eos_token_id) or None           # every EOS id counts (Llama-3.x-Instruct ships three)
     if eos_token_id is None:
@@ -338,10 +374,11 @@ def _run(self, input_ids, do_sample, warp, stopping_criteria, eos_token_id, gene
             shown["n"] = len(text)
 
     cb = on_step if (streamer is not None or tok is not None) else None
+    emit = request or None               # (an empty request returns the output object with sequences alone: the steps run as without it)
     if do_sample:
-        out = dec.sample(prompt, max_length, warp=warp, eos_token_id=eos_token_id, rng=random, on_step=cb, controls=controls)
+        out = dec.sample(prompt, max_length, warp=warp, eos_token_id=eos_token_id, rng=random, on_step=cb, controls=controls, emit=emit)
     else:
-        out = dec.greedy(prompt, max_length, eos_token_id=eos_token_id, rng=random, on_step=cb, controls=controls)
+        out = dec.greedy(prompt, max_length, eos_token_id=eos_token_id, rng=random, on_step=cb, controls=controls, emit=emit)
     if CONFIG_MAP.get("DEBUG", 0) and rank0:
         print("\n==========================ACCELERATION===SUMMARY======================================")
         print("Generated tokens: ", out.generated, "Total steps: ", out.steps, " Compression ratio: ", round(out.generated / max(out.steps, 1), 2))
@@ -349,21 +386,22 @@ def _run(self, input_ids, do_sample, warp, stopping_criteria, eos_token_id, gene
     res = torch.tensor([out.tokens], dtype=input_ids.dtype, device=input_ids.device)
     if streamer is not None:
         streamer.end()
-    return res
+    return res if request is None else generate_output(res, out, request)
 
 
 def jacobi_greedy_search_multilevel(self, input_ids, logits_processor=None, stopping_criteria=None, max_length=None, pad_token_id=None,
                                     eos_token_id=None, output_attentions=None, output_hidden_states=None, output_scores=None,
                                     return_dict_in_generate=None, synced_gpus=False, streamer=None, chat=False, stop_token=None,
-                                    generation_config=None, **model_kwargs):
-    """Same call contract as lade/decoding.py:697-715 (extras `chat`, `stop_token`); returns LongTensor [1, len]."""
-    assert not return_dict_in_generate, "return_dict_in_generate is not supported (lade/decoding.py:967)"
+                                    generation_config=None, output_logits=None, **model_kwargs):
+    """Same call contract as lade/decoding.py:697-715 (extras `chat`, `stop_token`); returns LongTensor [1, len], or with
+    return_dict_in_generate HF's GenerateDecoderOnlyOutput with `scores` / `logits` (the reference asserts that off, :967)."""
+    request = output_request(generation_config, return_dict_in_generate, output_scores, output_logits, output_attentions, output_hidden_states)
     controls, logits_processor = controls_from_processors(logits_processor)       # repetition penalty / min length run on the device
     assert logits_processor is None or len(logits_processor) == 0, "logits processors are not supported in greedy lookahead (:968)"
     if max_length is not None:
         from transformers.generation.stopping_criteria import MaxLengthCriteria, StoppingCriteriaList
         stopping_criteria = StoppingCriteriaList(list(stopping_criteria or []) + [MaxLengthCriteria(max_length)])
-    return _run(self, input_ids, False, None, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls)
+    return _run(self, input_ids, False, None, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls, request)
 
 
 def _canonical_warper(warpers, T_cls, K_cls, P_cls):
@@ -390,10 +428,11 @@ def _canonical_warper(warpers, T_cls, K_cls, P_cls):
 def jacobi_sample_multilevel(self, input_ids, logits_processor=None, stopping_criteria=None, logits_warper=None, max_length=None,
                              pad_token_id=None, eos_token_id=None, output_attentions=None, output_hidden_states=None, output_scores=None,
                              return_dict_in_generate=None, synced_gpus=False, streamer=None, chat=False, generation_config=None,
-                             controls=None, **model_kwargs):
+                             controls=None, output_logits=None, **model_kwargs):
     """Same call contract as lade/decoding.py:137-154.  Warpers are restricted like the reference (:375-377); repetition penalty and
-    min length among the logits processors run on the device (`controls`: already split off by _sample_proxy)."""
-    assert not return_dict_in_generate
+    min length among the logits processors run on the device (`controls`: already split off by _sample_proxy).  With
+    return_dict_in_generate: GenerateDecoderOnlyOutput, `scores` = the warped rows (the reference asserts that off at the head of its loop)."""
+    request = output_request(generation_config, return_dict_in_generate, output_scores, output_logits, output_attentions, output_hidden_states)
     if controls is None:
         controls, _ = controls_from_processors(logits_processor)
     from transformers.generation.logits_process import TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper
@@ -413,7 +452,7 @@ def jacobi_sample_multilevel(self, input_ids, logits_processor=None, stopping_cr
                 scores = wp(input_ids, scores)
             return scores
 
-    return _run(self, input_ids, True, warp, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls)
+    return _run(self, input_ids, True, warp, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls, request)
 
 
 def greedy_search_proxy(self, *args, **kwargs):
@@ -442,7 +481,7 @@ def _sample_proxy(self, input_ids, logits_processor=None, stopping_criteria=None
         return FUNC_MAP["_sample"](self, input_ids, logits_processor=logits_processor, stopping_criteria=stopping_criteria,
                                    generation_config=generation_config, synced_gpus=synced_gpus, streamer=streamer, **model_kwargs)
     chat = bool(int(os.environ.get("CHAT", 0)))
-    assert not generation_config.return_dict_in_generate, "return_dict_in_generate is not supported"
+    output_request(generation_config)            # (refuses attentions / hidden states before any work; the two loops read the flags themselves)
     if generation_config.do_sample:
         from transformers.generation.logits_process import TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper
         controls, warpers = controls_from_processors(logits_processor)      # processors first, then the warpers (HF's order)

@@ -487,3 +487,41 @@ def gen_argmax(logits: torch.Tensor, n_inp: int, gs: int, gen: torch.Tensor, ctl
     else:
         assert rows_out.dtype == torch.float32 and rows_out.is_contiguous() and rows_out.numel() >= (rows - n_inp) * V
         call("lade_gen_rows", *args, ptr(rows_out))
+
+
+# ---- emitted rows (per-token scores / logits of generate(); include/lade_hip.h "emitted rows") ------------------------------------
+def emit_init(desc: torch.Tensor, scores: Optional[torch.Tensor], logits: Optional[torch.Tensor], V: int) -> None:
+    """Points the device descriptor (int64 [cabi.EMIT_WORDS]) at the fp32 [cap_rows, V] destination buffers (either may be None) and
+    zeroes its row counter: once per generate() call, captured steps keep reading the same descriptor."""
+    assert desc.dtype == torch.int64 and desc.numel() >= cabi.EMIT_WORDS
+    cap = None
+    for name, t in (("scores", scores), ("logits", logits)):
+        if t is not None:
+            _dev(t, name)
+            assert t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.shape[1] == V, (name, t.shape, t.dtype)
+            assert cap is None or cap == t.shape[0]
+            cap = t.shape[0]
+    call("lade_emit_init", ptr(desc), ptr(scores), ptr(logits), 0 if cap is None else cap, V)
+
+
+def emit_rows(desc: torch.Tensor, raw: torch.Tensor, n_inp: int, gs: int, proc: Optional[torch.Tensor] = None, ctl: Optional[torch.Tensor] = None,
+              idx=None) -> None:
+    """Appends the rows of the tokens one step emitted to the descriptor's buffers (lade_emit_rows).  raw: the step's logits [out | n_inp
+    window rows | candidate rows] in the model dtype; proc: the processed fp32 rows [out | candidate rows] that become `scores` (None: the
+    widened raw rows).  idx None: count and candidate are read from ctl on the device (greedy); else a host sequence, one entry per token:
+    the candidate that supplied it (entry 0 is the out row's and is ignored)."""
+    _dev(raw, "raw")
+    assert raw.dim() == 2 and raw.stride(1) == 1 and desc.dtype == torch.int64
+    if proc is not None:
+        assert proc.dtype == torch.float32 and proc.dim() == 2 and proc.stride(1) == 1 and proc.shape[1] == raw.shape[1]
+    if idx is None:
+        need = None              # decided on the device: the caller's candidate rows are those the post-step verified
+        harr, n_idx = None, 0
+    else:
+        n_idx = len(idx)
+        need = (0 if n_idx <= 1 else max(int(c) for c in idx[1:]) * gs + n_idx - 1)
+        harr = host_ids(idx)
+    if need is not None and (raw.shape[0] < 1 + (n_inp + need if need else 0) or (proc is not None and proc.shape[0] < 1 + need)):
+        raise cabi.LadeHipError(f"emit_rows: candidate row {need} lies outside the step's rows (raw {tuple(raw.shape)}, n_inp={n_inp})")
+    call("lade_emit_rows", ptr(desc), ptr(raw), raw.stride(0), dtype_code(raw), n_inp, gs, ptr(proc), 0 if proc is None else proc.stride(0),
+         ptr(ctl), harr, n_idx, raw.shape[1])
