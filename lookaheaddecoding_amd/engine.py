@@ -21,16 +21,15 @@ read only); wider steps (prefill chunks) and fp32 use the library on the row-maj
 """
 from __future__ import annotations
 
-import json
 import math
 import os
-import sys
 from typing import Dict, List, Optional, Sequence
 
 import torch
 
 from . import cabi, ops
 from .ops import StepMask
+from .tuning import KernelDecisions, shipped_tune_table, use_prefill_attn
 
 
 def rope_inv_freq(d: int, theta: float, scaling: Optional[dict] = None) -> torch.Tensor:
@@ -94,10 +93,6 @@ def _on_device(fn):
         with torch.cuda.device(dev):
             return fn(self, *a, **k)
     return wrapped
-
-
-from .tuning import (KernelDecisions, use_prefill_attn, REP_ROWS, _STEP_TUNE_CACHE, _STEP_TUNE_LOCK, _TUNE_CACHE, _TUNE_LOCK, _TUNE_RANKED, _TUNE_TIMES,  # noqa: F401 (re-exported: tests / tools)
-                     gpu_identity, shipped_tune_table)
 
 
 class StepEngine(KernelDecisions):
@@ -455,23 +450,15 @@ class StepEngine(KernelDecisions):
         if T > self.max_T or P + T > self.S_max:
             raise cabi.LadeHipError(f"step of T={T} tokens at P={P} exceeds the engine limits (max_T={self.max_T}, S_max={self.S_max})")
         H, Hkv, d = self.H, self.Hkv, self.d
-        x, h, r = self.ws_x[:T], self.ws_h[:T], self.ws_r[:T]
+        mclass = self.row_class(T) if self.custom_gemm else None
+        fused = mclass is not None
+        if fused:           # BEFORE this call touches a workspace; raises during a stream capture: a graph must never bake a table that later eager steps do not use
+            self._decide(mclass)
+        x, h, r = self.ws_x[:T], self.ws_h[:T], self.ws_r[:T]            # (sliced after the gate: its probe may have grown the workspaces)
         qkv, o, gu, a = self.ws_qkv[:T], self.ws_o[:T], self.ws_gu[:T], self.ws_a[:T]
-        fused = self.custom_gemm and T <= self.ROW_CLASSES[-1]
-        if fused and not self._refining:
-            mclass = next(c for c in self.ROW_CLASSES if T <= c)
-            if mclass not in self._refined:          # once per row class: the decisions re-taken INSIDE a step - BEFORE this call touches a workspace
-                for n in self.LAYER_GEMMS:
-                    self._tune(n, mclass)
-                self._refine_in_step(mclass)         # (raises during a stream capture: a graph must never bake a table that later eager steps do not use)
-                x, h, r = self.ws_x[:T], self.ws_h[:T], self.ws_r[:T]            # (the probe may have grown the workspaces)
-                qkv, o, gu, a = self.ws_qkv[:T], self.ws_o[:T], self.ws_gu[:T], self.ws_a[:T]
-        cfg_qkv = self._tune("wqkv", T) if fused else None
-        cfg_o = self._tune("wo", T) if fused else None
-        cfg_gu = self._tune("wgu", T) if fused else None
-        cfg_d = self._tune("wd", T) if fused else None
+        cfg_qkv, cfg_o, cfg_gu, cfg_d = [self._tune(n, mclass) for n in self.LAYER_GEMMS] if fused else [None] * 4
         # the attention launch of this row class: the work-group shape, the split rule
-        acfg = (self.attn_cfg.get(next(c for c in self.ROW_CLASSES if T <= c), self.attn_default) if fused else (0, 0, 0))
+        acfg = self.attn_cfg.get(mclass, self.attn_default) if fused else (0, 0, 0)
         if n_splits is None:
             n_splits = self.n_splits_for(T, P + T, choice=acfg if fused else None)
         # causal chunks above the last row class (the ones on the library GEMMs): the one-pass prefill kernel instead of the split-KV pair
@@ -492,14 +479,14 @@ class StepEngine(KernelDecisions):
             else:
                 ops.add_rmsnorm(x, r, lw["ln1"], self.eps, out=h)
             if cfg_qkv:
-                ops.gemm_parts(h, self._w(lw, "wqkv"), part, cfg_qkv[2], cfg_qkv[1], cfg_qkv[0], cfg_qkv[3], cfg_qkv[4], cfg_qkv[5])
+                cfg_qkv.gemm_parts(h, self._w(lw, "wqkv"), part)
                 qb = self.ws_q[:T]
                 if self.skip_attn != "all":
                     if lw["epi_parts"] is not None:
-                        ops.rope_kv_append_parts_ex(part, cfg_qkv[2], qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d,
+                        ops.rope_kv_append_parts_ex(part, cfg_qkv.n_split, qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d,
                                                     dyn_P=dyn_P, epi=lw["epi_parts"])
                     else:
-                        ops.rope_kv_append_parts(part, cfg_qkv[2], qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P)
+                        ops.rope_kv_append_parts(part, cfg_qkv.n_split, qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P)
                 q_in = qb
             else:
                 if "bqkv" in lw:                  # F.linear with a bias: one rounding of (h W^T + b)
@@ -531,22 +518,22 @@ class StepEngine(KernelDecisions):
                 e1.record()
                 ev.append((e0, e1, mask.T, 0 if pf_attn else n_splits))       # 0 splits = the one-pass prefill kernel ran
             if cfg_o:
-                ops.gemm_parts(o, self._w(lw, "wo"), part, cfg_o[2], cfg_o[1], cfg_o[0], cfg_o[3], cfg_o[4], cfg_o[5])
-                ops.add_rmsnorm_parts(x, part, cfg_o[2], lw["ln2"], self.eps, out=h)      # x += attn; h = norm(x)
+                cfg_o.gemm_parts(o, self._w(lw, "wo"), part)
+                ops.add_rmsnorm_parts(x, part, cfg_o.n_split, lw["ln2"], self.eps, out=h)      # x += attn; h = norm(x)
             else:
                 torch.matmul(o, self._row(lw, "wo").t(), out=r)
                 ops.add_rmsnorm(x, r, lw["ln2"], self.eps, out=h)
-            if cfg_gu and cfg_gu[2] == 1:                 # gate/up GEMM + SwiGLU in one launch
-                ops.gemm_swiglu(h, self._w(lw, "wgu"), a, cfg_gu[1], cfg_gu[0], cfg_gu[3], cfg_gu[4], cfg_gu[5])
+            if cfg_gu and cfg_gu.swiglu_fused:            # gate/up GEMM + SwiGLU in one launch
+                cfg_gu.gemm_swiglu(h, self._w(lw, "wgu"), a)
             elif cfg_gu:
-                ops.gemm_parts(h, self._w(lw, "wgu"), part, cfg_gu[2], cfg_gu[1], cfg_gu[0], cfg_gu[3], cfg_gu[4], cfg_gu[5])
-                ops.silu_mul_parts(part, cfg_gu[2], T, self.inter, out=a, layout=self.gu_layout)
+                cfg_gu.gemm_parts(h, self._w(lw, "wgu"), part)
+                ops.silu_mul_parts(part, cfg_gu.n_split, T, self.inter, out=a, layout=self.gu_layout)
             else:
                 torch.matmul(h, self._row(lw, "wgu").t(), out=gu)
                 ops.silu_mul(gu, out=a, layout=self.gu_layout)
             if cfg_d:
-                ops.gemm_parts(a, self._w(lw, "wd"), part, cfg_d[2], cfg_d[1], cfg_d[0], cfg_d[3], cfg_d[4], cfg_d[5])
-                r_parts = cfg_d[2]
+                cfg_d.gemm_parts(a, self._w(lw, "wd"), part)
+                r_parts = cfg_d.n_split
             else:
                 torch.matmul(a, self._row(lw, "wd").t(), out=r)
                 r_parts = 0
@@ -560,13 +547,11 @@ class StepEngine(KernelDecisions):
         cfg_lm = self._tune("lm_head", n_sel) if (self.custom_gemm and n_sel <= self.ROW_CLASSES[-1] and self.V % 8 == 0) else None
         w_lm = self._lm_kt if self._lm_kt is not None else self._lm_head
         if cfg_lm and argmax_out is not None and n_sel <= 128 and cabi.debug("fuse_tail", "1") != "0":
-            nb = (self.V + cfg_lm[1] - 1) // cfg_lm[1]
-            pairs = torch.empty(n_sel * nb * 2, dtype=torch.float32, device=self.device)
-            ops.gemm_argmax(hn, w_lm, argmax_out, pairs, bn=cfg_lm[1], mb=cfg_lm[0], mt=cfg_lm[3], nt=cfg_lm[4], ring=cfg_lm[5])
+            cfg_lm.gemm_argmax(hn, w_lm, argmax_out)             # (allocates its n_sel x column-blocks pair buffer)
             return None
         if cfg_lm:
             logits = torch.empty(n_sel, self.V, dtype=self.dtype, device=self.device)
-            ops.gemm_skinny(hn, w_lm, out=logits, n_split=1, bn=cfg_lm[1], mb=cfg_lm[0], mt=cfg_lm[3], nt=cfg_lm[4], ring=cfg_lm[5])
+            cfg_lm.gemm_skinny(hn, w_lm, logits)
         else:
             logits = torch.matmul(hn, self._lm_head.t())
         if argmax_out is not None:

@@ -28,6 +28,7 @@ import torch
 import torch.distributed as dist
 
 from .decoding import StepShape, capture_step_graph, generate_loop, step_shape
+from .tuning import GemmCfg
 
 REC_HEAD = 4           # first_guess, n_inp, g_local, (reserved)
 
@@ -147,7 +148,7 @@ class RcclComm:
 
 
 # ---- rank 0's GEMM autotune table as a fixed int32 block (so that it can travel through the step's own all-gather) ----
-_TUNE_FIELDS = 7           # present flag + (mb, bn, S, mt, nt, ring)
+_TUNE_FIELDS = 1 + len(GemmCfg._fields)           # present flag + the decision (an `attn:<class>` row: (0, work-group rows, split mode, 0, 0, 0))
 
 
 def encode_tune_table(table: dict, names: Sequence[str], classes: Sequence[int]) -> List[int]:

@@ -10,7 +10,8 @@ from __future__ import annotations
 import json
 import os
 import sys
-from typing import Optional, Sequence
+import threading
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -31,13 +32,142 @@ def shipped_tune_table(device) -> str:
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned", f"{arch}_{n_cu}cu.json")
 
 
-_TUNE_CACHE: dict = {}
-_TUNE_TIMES: dict = {}
-_TUNE_RANKED: dict = {}
-_TUNE_LOCK = __import__("threading").Lock()
-_STEP_TUNE_CACHE: dict = {}
-_STEP_TUNE_LOCK = __import__("threading").Lock()
+_TUNE_CACHE: dict = {}           # isolated pass, per (shape, row class, ...) and process: (winner, its ms, [(ms, cfg | None)] fastest first)
+_TUNE_LOCK = threading.Lock()
+_STEP_TUNE_CACHE: dict = {}      # in-step pass: (choice per projection + "attn", log)
+_STEP_TUNE_LOCK = threading.Lock()
 REP_ROWS = {32: 30, 64: 60, 96: 92, 128: 128, 160: 156, 192: 180, 256: 240}        # the rows a row class is timed at
+LDS_BYTES = 160 * 1024           # per CU: what the ring of (weight rows + activation rows) x 128-byte stages of a GEMM work-group must fit
+
+
+class GemmCfg(NamedTuple):
+    """One GEMM decision: the launch parameters of the weight-streaming kernel (csrc/gemm_kernel.hpp).  A plain tuple in the tune files, the
+    table lookahead-parallel ranks exchange and bench.py's report; `None` in its place = the library GEMM."""
+    mb: int            # 32-row activation blocks per work-group (= row class / 32)
+    bn: int            # weight rows per work-group
+    n_split: int       # split-K partials (1 = unsplit: the output is written once, in the model dtype)
+    mt: int            # m-blocks per wave
+    nt: int            # n-tiles per wave (0 = fewest)
+    ring: int = 0      # stages of the LDS ring (0 = the shape's default depth)
+
+    @property
+    def stage_bytes(self) -> int:
+        return (self.bn + 32 * self.mb) * 128
+
+    @property
+    def swiglu_fused(self) -> bool:
+        """of a gate/up decision: the unsplit variant that carries SwiGLU in its epilogue (no partials, no SwiGLU launch)"""
+        return self.n_split == 1
+
+    # the one place each launch kind's argument order is written
+    def gemm_parts(self, a, w, part) -> None:
+        ops.gemm_parts(a, w, part, self.n_split, self.bn, self.mb, self.mt, self.nt, self.ring)
+
+    def gemm_swiglu(self, a, w_gu, out) -> None:
+        ops.gemm_swiglu(a, w_gu, out, self.bn, self.mb, self.mt, self.nt, self.ring)
+
+    def gemm_skinny(self, a, w, out) -> None:
+        ops.gemm_skinny(a, w, out=out, n_split=1, bn=self.bn, mb=self.mb, mt=self.mt, nt=self.nt, ring=self.ring)
+
+    def gemm_argmax(self, a, w, out) -> None:
+        ops.gemm_argmax(a, w, out, bn=self.bn, mb=self.mb, mt=self.mt, nt=self.nt, ring=self.ring)
+
+
+# ---- what the tuners time: pure functions of the shape, in the order they are timed (ties and the short lists depend on it) ----
+# per row class: (m-blocks per work-group, m-blocks per wave, n-tiles per wave (0 = fewest), weight rows per work-group)
+SPLITK_SHAPES = {
+    32: ((1, 1, 0, (64, 128, 256)), (1, 1, 2, (128, 256)), (2, 1, 0, (128,)), (1, 1, 1, (96,))),
+    64: ((2, 1, 0, (128, 256)), (2, 2, 0, (128, 192, 256)), (2, 2, 2, (192, 256)), (2, 1, 1, (64, 96)), (2, 2, 1, (96,))),
+    96: ((3, 1, 0, (64, 128, 192, 256)), (3, 3, 0, (128, 192, 256)), (3, 3, 2, (192, 256)), (4, 1, 0, (128, 192)), (4, 2, 0, (128, 192)),
+         (3, 3, 1, (96,))),
+    128: ((4, 1, 0, (64, 128, 192, 256)), (4, 2, 0, (128, 192, 256)), (4, 4, 0, (192, 256)), (4, 4, 2, (192, 256)), (4, 4, 1, (96,)),
+          (4, 2, 1, (96,))),
+    # 160 rows (round 6; config 4's steps with 2..6 candidates, 132..156 rows, padded to 192 before): one wave holds all five
+    # m-blocks (5 is prime), the waves lie along N - up to 256 weight rows beside the 20 KB activation tile, three stages
+    160: ((5, 5, 1, (96, 128, 192, 256)), (5, 5, 2, (128, 256))),
+    # 192 / 256 rows (config 4's 120 + 6g-token steps, hot-regime steps): the activation tile alone is 24 / 32 KB per stage,
+    # so the weight tile stays at <= 128 rows for the 3-stage ring to fit the 160 KB of LDS
+    192: ((6, 3, 1, (64, 128)), (6, 3, 2, (128,)), (6, 2, 1, (64,)), (6, 2, 2, (128,))),
+    256: ((8, 4, 1, (64, 128)), (8, 4, 2, (128,)), (8, 2, 1, (64,)), (8, 2, 2, (128,)))}
+
+
+def splitk_candidates(mclass: int, N: int, K: int, n_cu: int) -> list:
+    """the split-K shapes of a row class x the split counts that cover the CUs once, twice and three times"""
+    out = []
+    for mb, mt, nt, bns in SPLITK_SHAPES[mclass]:
+        for bn in bns:
+            nblk = (N + bn - 1) // bn
+            for S in sorted({max(1, round(n_cu * k / nblk)) for k in (1, 2, 3)}):
+                if 2 <= S <= 16 and K // 64 >= 2 * S and S * mclass <= 16 * 128:       # the partial workspace holds 16 x 128 rows (of the CLASS maximum)
+                    out.append(GemmCfg(mb, bn, S, mt, nt))
+    return out
+
+
+def swiglu_candidates(mclass: int, N: int) -> list:
+    """gate/up without split-K: BN weight rows x the whole K per work-group, SwiGLU in the epilogue, output in the model dtype.  Needs
+    N / BN work-groups to cover the CUs on their own: 96-row blocks at the 7B / 13B widths."""
+    mbs = mclass // 32
+    return [GemmCfg(mbs, bn, 1, mt, 1)
+            for bn in (64, 96, 128) + ((224,) if N % 224 == 0 else ())        # 224: N = 256 x 224 at the 70B width
+            for mt in sorted({1, 2 if mbs % 2 == 0 else 1, mbs if mbs <= 5 else mbs // 2})
+            if mbs % mt == 0 and (mbs // mt) * (bn // 32) <= 8]
+
+
+def lm_head_candidates(mclass: int) -> list:
+    mbs = mclass // 32
+    return [GemmCfg(mbs, bn, 1, mt, nt) for bn in (64, 96, 128, 192, 256) for mt in sorted({1, mbs if mbs <= 5 else mbs // 2}) for nt in (0, 1, 2)
+            if mbs % mt == 0]
+
+
+def ring_variants(cfg: GemmCfg, in_step: bool) -> list:
+    """`cfg` at the other ring depths the kernel is compiled for (2, 3, 4 = default, 5, 6, 8) that fit the LDS; the default depth is only ever
+    spelled 0.  The isolated pass tries 3, 5, 6, 8 around its short list; the in-step pass also the default itself and, for stages of >= 32 KB
+    only, a DOUBLE buffer (the 160-row class and wider: two stages beat three on 13B gate/up at 256 weight rows + 160 activation rows, 68.9 vs
+    71.7 us isolated, and the in-step pass picks them for all four projections of the 13B 192-row class, profiles/r6_rows_curve_13b.txt)"""
+    stage = cfg.stage_bytes
+    default = min(4, LDS_BYTES // stage)           # what ring = 0 stands for
+    depths = (3, 5, 6, 8) if not in_step else (0, 3, 5, 6, 8) + ((2,) if stage >= 32 * 1024 else ())
+    return [cfg._replace(ring=r) for r in depths if r == 0 or (r != default and r * stage <= LDS_BYTES)]
+
+
+def time_launches(fn, warmup: int, reps: int) -> float:
+    """ms per launch of fn(i), best of two rounds (the winner must not be a timing fluke); round r launches i = r .. r + reps - 1"""
+    best_t = float("inf")
+    for rnd in range(2):
+        for i in range(warmup):
+            fn(i)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(reps):
+            fn(i + rnd)
+        e1.record()
+        torch.cuda.synchronize()
+        best_t = min(best_t, e0.elapsed_time(e1) / reps)
+    return best_t
+
+
+def _time_each(cands, ms_of) -> list:
+    """[(ms, cfg)] of the candidates the library has a kernel for (a wave grid that is not built for the row class raises)"""
+    timed = []
+    for c in cands:
+        try:
+            timed.append((ms_of(c), c))
+        except cabi.LadeHipError:
+            continue
+    return timed
+
+
+def _winner(what: str, N: int, K: int, t_lib: float, timed: list, n_top: int):
+    """(the fastest of `timed` | None = the library unless one beats it, its ms)"""
+    best, t_best = None, t_lib
+    if timed and min(timed)[0] < t_lib:
+        t_best, best = min(timed)
+    if cabi.debug("tune_verbose"):          # tools/gemm_tune_probe.py: what the tuner saw
+        top = " ".join(f"{tuple(c)}:{t * 1e3:.1f}" for t, c in sorted(timed)[:n_top])
+        print(f"[tune] {what} N={N} K={K} lib {t_lib * 1e3:.1f} us | best {best and tuple(best)} {t_best * 1e3:.1f} us "
+              f"({N * K * 2 / 1e6 / (t_best * 1e3):.2f} TB/s) | {top}", file=sys.stderr, flush=True)
+    return best, t_best
 
 
 PREFILL_ATTN_WG_ROWS = 256       # query rows of the (head-in-group, token) row space per work-group of lade_attn_prefill (csrc/attn_prefill.hip)
@@ -88,14 +218,27 @@ class KernelDecisions:
         the same kernels (16-bit partials round alike)."""
         if self.dtype == torch.float32:
             return (0, 0, 0)
-        mclass = next((c for c in self.ROW_CLASSES if T <= c), None)
+        mclass = self.row_class(T)
         if mclass is None or not self.custom_gemm:
             return (0, 128, 0)
-        if mclass not in self._refined and not self._refining and not torch.cuda.is_current_stream_capturing():
-            for n in self.LAYER_GEMMS:
-                self._tune(n, mclass)
-            self._refine_in_step(mclass)
+        self._decide(mclass, skip_in_capture=True)
         return self.attn_cfg.get(mclass, self.attn_default)
+
+    def row_class(self, T: int) -> Optional[int]:
+        """the row class a T-row step runs in (None above the last one: the library GEMMs)"""
+        return next((m for m in self.ROW_CLASSES if T <= m), None)
+
+    def _decide(self, mclass: int, *, allow_grow: bool = False, skip_in_capture: bool = False) -> None:
+        """The one gate of forward(), attn_choice(), prepare() and tune_all(): takes the decisions of a row class that is still open - the
+        isolated pass of the four layer projections, then the in-step pass.  The isolated pass must be over before a step writes its first
+        workspace - _tune_timed uses `ws_part` as its scratch - so forward() calls this before anything else, also for the models
+        _step_tunable() rejects (whose in-step pass only closes the class).  allow_grow: the probe may re-allocate the workspaces (construction
+        time only); skip_in_capture: attn_choice only asks, and gets the present answer during a stream capture - a step gets _refine_in_step's error."""
+        if mclass in self._refined or self._refining or not self.custom_gemm or (skip_in_capture and torch.cuda.is_current_stream_capturing()):
+            return
+        for n in self.LAYER_GEMMS:
+            self._tune(n, mclass)
+        self._refine_in_step(mclass, allow_grow)
 
     def n_splits_for(self, T: int, S_tot: int, choice=None) -> int:
         if self.dtype == torch.float32:
@@ -106,7 +249,7 @@ class KernelDecisions:
         # always the split + merge form, and never fewer splits than a 1024-key cache would get: the hipGraph steps are
         # captured with exactly that rule, and an eager step of the same (short) sequence must round the same way
         # (16-bit partials) for the two modes to produce the same token stream
-        _fuse, wg, mode = choice if choice is not None else self.attn_choice(T)
+        _, wg, mode = choice if choice is not None else self.attn_choice(T)
         return min(ops.choose_splits(self.H, self.H // self.Hkv, T, max(S_tot, 1024), self.n_cu, allow_single=False,
                                      block_rows=0 if wg in (0, 128) else wg, mode=mode), self.max_splits)
 
@@ -157,7 +300,7 @@ class KernelDecisions:
             for n in self.GEMM_NAMES:
                 if n in row:
                     v = row[n]
-                    self.gemm_cfg[(n, m)] = None if v is None else tuple(int(x) for x in v)
+                    self.gemm_cfg[(n, m)] = None if v is None else GemmCfg(*(int(x) for x in v))
             if "attn" in row:
                 if int(row["attn"][0]) != 0:        # the slot of the fused RoPE + KV append forms (removed: DESIGN 4.9)
                     raise cabi.LadeHipError(f"LADE_TUNE_FILE={path}: row class {m} selects a fused-RoPE attention form ({row['attn'][:3]}), which this library no longer has")
@@ -205,87 +348,46 @@ class KernelDecisions:
 
     # ---- GEMM selection ---------------------------------------------------------------------------
     def _tune(self, name: str, M: int):
-        """(mb, bn, n_split, mt, nt, ring) of the split-K GEMM for projection `name` at a step of M rows, or None when the library
+        """the GemmCfg of the hand-written GEMM for projection `name` at a step of M rows, or None when the library
         GEMM is faster.  Timed once per (projection, row class) on this GPU, rotating through the layers' weights so the
         stream comes from HBM rather than from the Infinity Cache."""
-        mclass = next(c for c in self.ROW_CLASSES if M <= c)
+        mclass = self.row_class(M)
         key = (name, mclass)
         if key in self.gemm_cfg:
             return self.gemm_cfg[key]
         if name == "lm_head":
-            ws = ([self._lm_head], [self._lm_kt if self._lm_kt is not None else self._lm_head])
+            ws_lib, ws = [self._lm_head], [self._lm_kt if self._lm_kt is not None else self._lm_head]
         else:         # (row-major: library GEMM - none when the weights are held K-tile-major only, what the skinny GEMM streams)
             # the library is a candidate for a decode-width step only when EVERY layer still holds the row-major weight (a layer whose
             # original was released would pay a rebuild per call)
             rows = [lw[name] for lw in self.layers if name in lw]
-            ws = (rows if len(rows) == self.L else None, [self._w(lw, name) for lw in self.layers])
-        N, K = self._nk(ws[1][0])
+            ws_lib, ws = rows if len(rows) == self.L else None, [self._w(lw, name) for lw in self.layers]
+        N, K = self._nk(ws[0])
         # one decision per (shape, row class, dtype) and process: engines of the same model (lookahead-parallel ranks run as
         # threads, a decoder rebuilt on the same weights) must pick the same kernel, or their 16-bit results round differently
         # (the gate/up decision differs from a plain projection of the same shape - SwiGLU tail cost, fused-epilogue variant - and
         # timings taken on one GPU model do not transfer to another)
         gkey = (int(N), int(K), mclass, str(self.dtype), name == "wgu", self.gu_layout if name == "wgu" else 0,
-                torch.cuda.get_device_name(self.device), self.n_cu, ws[1][0].dim() == 3, ws[0] is None, name == "lm_head")
+                torch.cuda.get_device_name(self.device), self.n_cu, ws[0].dim() == 3, ws_lib is None, name == "lm_head")
         with _TUNE_LOCK:
             if gkey not in _TUNE_CACHE:
-                self._tuned_ms, self._tuned_ranked = None, []
-                _TUNE_CACHE[gkey] = self._tune_timed(name, mclass, ws, N, K)
-                _TUNE_TIMES[gkey] = self._tuned_ms
-                _TUNE_RANKED[gkey] = self._tuned_ranked
-            best = _TUNE_CACHE[gkey]
-            self._ranked[key] = _TUNE_RANKED.get(gkey, [])
-            # what the winner took when it was timed (isolated launches, every launch on another layer's weights), for bench.py's report
-            self.gemm_times[key] = (_TUNE_TIMES.get(gkey), int(N) * int(K) * ws[1][0].element_size())
+                _TUNE_CACHE[gkey] = self._tune_timed(name, mclass, ws_lib, ws, N, K)
+            best, ms, self._ranked[key] = _TUNE_CACHE[gkey]
+        # what the winner took when it was timed (isolated launches, every launch on another layer's weights), for bench.py's report
+        self.gemm_times[key] = (ms, int(N) * int(K) * ws[0].element_size())
         self.gemm_cfg[key] = best
         if name == "lm_head" and self.tune_file:
             self.save_tune_file()
         return best
 
-    def _tune_timed(self, name: str, mclass: int, ws, N: int, K: int):
-        ws_lib, ws = ws
+    def _tune_timed(self, name: str, mclass: int, ws_lib, ws, N: int, K: int):
+        """-> (the fastest GemmCfg | None = the library, its ms, [(ms incl. the consumer tail, GemmCfg | None)] fastest first)"""
         a = torch.randn(REP_ROWS[mclass], K, device=self.device).to(self.dtype)
         out = torch.empty(a.shape[0], N, dtype=self.dtype, device=self.device)
         if name == "lm_head":
             return self._tune_lm_head(mclass, a, out, ws_lib, ws, N, K)
-        cands = []
-        # (m-blocks per work-group, m-blocks per wave, n-tiles per wave (0 = fewest), weight rows per work-group)
-        shapes = {32: ((1, 1, 0, (64, 128, 256)), (1, 1, 2, (128, 256)), (2, 1, 0, (128,)), (1, 1, 1, (96,))),
-                  64: ((2, 1, 0, (128, 256)), (2, 2, 0, (128, 192, 256)), (2, 2, 2, (192, 256)), (2, 1, 1, (64, 96)), (2, 2, 1, (96,))),
-                  96: ((3, 1, 0, (64, 128, 192, 256)), (3, 3, 0, (128, 192, 256)), (3, 3, 2, (192, 256)), (4, 1, 0, (128, 192)), (4, 2, 0, (128, 192)),
-                       (3, 3, 1, (96,))),
-                  128: ((4, 1, 0, (64, 128, 192, 256)), (4, 2, 0, (128, 192, 256)), (4, 4, 0, (192, 256)), (4, 4, 2, (192, 256)), (4, 4, 1, (96,)),
-                        (4, 2, 1, (96,))),
-                  # 160 rows (round 6; config 4's steps with 2..6 candidates, 132..156 rows, padded to 192 before): one wave holds all five
-                  # m-blocks (5 is prime), the waves lie along N - up to 256 weight rows beside the 20 KB activation tile, three stages
-                  160: ((5, 5, 1, (96, 128, 192, 256)), (5, 5, 2, (128, 256))),
-                  # 192 / 256 rows (config 4's 120 + 6g-token steps, hot-regime steps): the activation tile alone is 24 / 32 KB per stage,
-                  # so the weight tile stays at <= 128 rows for the 3-stage ring to fit the 160 KB of LDS
-                  192: ((6, 3, 1, (64, 128)), (6, 3, 2, (128,)), (6, 2, 1, (64,)), (6, 2, 2, (128,))),
-                  256: ((8, 4, 1, (64, 128)), (8, 4, 2, (128,)), (8, 2, 1, (64,)), (8, 2, 2, (128,)))}[mclass]
-        for mb, mt, nt, bns in shapes:
-            for bn in bns:
-                nblk = (N + bn - 1) // bn
-                for S in sorted({max(1, round(self.n_cu / nblk)), max(1, round(self.n_cu * 2 / nblk)), max(1, round(self.n_cu * 3 / nblk))}):
-                    if 2 <= S <= 16 and K // 64 >= 2 * S and S * mclass <= 16 * 128:       # the partial workspace holds 16 x 128 rows (of the CLASS maximum)
-                        cands.append((mb, bn, S, mt, nt))
-
-        def time_it(fn, reps=16):
-            best_t = float("inf")
-            for rnd in range(2):                       # best of two rounds: the winner must not be a timing fluke
-                for i in range(2):
-                    fn(i)
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for i in range(reps):
-                    fn(i + rnd)
-                e1.record()
-                torch.cuda.synchronize()
-                best_t = min(best_t, e0.elapsed_time(e1) / reps)
-            return best_t
-
         # what follows the GEMM inside the step: a split-K or library gate/up GEMM is followed by the SwiGLU kernel (~6 us with its
-        # launch boundary), the fused-epilogue variant (S = 1 below) is not
+        # launch boundary), the fused-epilogue variant is not
         # (a dependent launch ~2.5 us + its reads of the GEMM output at ~4 TB/s: 6.3 us measured behind 4 partials of the 7B shape
         # at 60 rows, ~9 us behind 2 partials of the 13B shape at 120 rows; times here are in ms)
         Mrows = a.shape[0]
@@ -295,109 +397,38 @@ class KernelDecisions:
         if name != "wgu" and cabi.debug("tune_consumer"):          # experiment: the consumer's read of the partials, every projection
             rate = float(cabi.debug("tune_consumer")) * 1e9
             tail = lambda out_bytes: out_bytes / rate
+        act = torch.empty(Mrows, N // 2, dtype=self.dtype, device=self.device) if name == "wgu" and self.gu_layout == 1 else None
+        ms = lambda fn: time_launches(fn, warmup=2, reps=16)
+
+        def ms_of(c):
+            if c.swiglu_fused:
+                return ms(lambda i: c.gemm_swiglu(a, ws[i % len(ws)], act))
+            return ms(lambda i: c.gemm_parts(a, ws[i % len(ws)], self.ws_part)) + tail(c.n_split * Mrows * N * 4)
         # + the consumer's extra read; K-tile-only weights: the library would need its row-major operand rebuilt per call - not a candidate
-        t_lib = float("inf") if ws_lib is None else time_it(lambda i: torch.matmul(a, ws_lib[i % len(ws_lib)].t(), out=out)) + 0.003 + tail(Mrows * N * 2)
-        timed = []                        # (ms incl. the consumer tail, (mb, bn, S, mt, nt, ring))
-        for (mb, bn, S, mt, nt) in cands:
-            t = time_it(lambda i: ops.gemm_parts(a, ws[i % len(ws)], self.ws_part, S, bn, mb, mt, nt)) + tail(S * Mrows * N * 4)
-            timed.append((t, (mb, bn, S, mt, nt, 0)))
-        act = None
-        if name == "wgu" and self.gu_layout == 1:
-            # no split-K: BN weight rows x the whole K per work-group, SwiGLU in the epilogue, output in the model dtype.  Needs
-            # N / BN work-groups to cover the CUs on their own: 96-row blocks at the 7B / 13B widths.
-            act = torch.empty(a.shape[0], N // 2, dtype=self.dtype, device=self.device)
-            mbs = mclass // 32
-            for bn in (64, 96, 128) + ((224,) if N % 224 == 0 else ()):        # 224: N = 256 x 224 at the 70B width
-                for mt in sorted({1, 2 if mbs % 2 == 0 else 1, mbs if mbs <= 5 else mbs // 2}):
-                    if mbs % mt or (mbs // mt) * (bn // 32) > 8:
-                        continue
-                    try:
-                        t = time_it(lambda i: ops.gemm_swiglu(a, ws[i % len(ws)], act, bn, mbs, mt, 1))
-                    except cabi.LadeHipError:
-                        continue                      # wave grid not built for this row class
-                    timed.append((t, (mbs, bn, 1, mt, 1, 0)))
+        t_lib = float("inf") if ws_lib is None else ms(lambda i: torch.matmul(a, ws_lib[i % len(ws_lib)].t(), out=out)) + 0.003 + tail(Mrows * N * 2)
+        timed = [(ms_of(c), c) for c in splitk_candidates(mclass, N, K, self.n_cu)]
+        if act is not None:
+            timed += _time_each(swiglu_candidates(mclass, N), ms_of)
         # second pass: the LDS ring depth of the best few.  More stages = more bytes in flight per work-group, fewer work-groups per CU;
         # which of the two a projection needs depends on its split count (an unsplit gate/up GEMM is one work-group per CU whatever the
         # ring costs, a 512-work-group split-K launch needs two per CU), so the depth is a per-kernel decision like the shape itself
         if cabi.debug("tune_ring", "0") != "0":      # (off: isolated launches do not rank ring depths the way the step does - _refine_in_step decides them)
-            for t0, (mb, bn, S, mt, nt, _r) in sorted(timed)[:3]:
-                stage_bytes = (bn + 32 * mb) * 128
-                for ring in (3, 5, 6, 8):
-                    if ring * stage_bytes > 160 * 1024 or ring == min(4, 160 * 1024 // stage_bytes):
-                        continue
-                    try:
-                        if S == 1:
-                            t = time_it(lambda i: ops.gemm_swiglu(a, ws[i % len(ws)], act, bn, mb, mt, nt, ring))
-                        else:
-                            t = time_it(lambda i: ops.gemm_parts(a, ws[i % len(ws)], self.ws_part, S, bn, mb, mt, nt, ring)) + tail(S * Mrows * N * 4)
-                    except cabi.LadeHipError:
-                        continue
-                    timed.append((t, (mb, bn, S, mt, nt, ring)))
-        best, t_best = None, t_lib
-        if timed and min(timed)[0] < t_lib:
-            t_best, best = min(timed)
-        self._tuned_ms = t_best
-        self._tuned_ranked = sorted(timed) + ([(t_lib, None)] if ws_lib is not None else [])
-        if cabi.debug("tune_verbose"):          # tools/gemm_tune_probe.py: what the tuner saw
-            mbytes = N * K * ws[0].element_size() / 1e6
-            top = " ".join(f"{c}:{t * 1e3:.1f}" for t, c in sorted(timed)[:6])
-            print(f"[tune] {name}:{mclass} rows={Mrows} N={N} K={K} lib {t_lib * 1e3:.1f} us | best {best} {t_best * 1e3:.1f} us "
-                  f"({mbytes / (t_best * 1e3):.2f} TB/s) | {top}", file=sys.stderr, flush=True)
-        return best
+            timed += _time_each([r for _t, c in sorted(timed)[:3] for r in ring_variants(c, in_step=False)], ms_of)
+        best, t_best = _winner(f"{name}:{mclass} rows={Mrows}", N, K, t_lib, timed, 6)
+        return best, t_best, sorted(timed) + ([(t_lib, None)] if ws_lib is not None else [])
 
     def _tune_lm_head(self, mclass: int, a, out, ws_lib, ws, N: int, K: int):
         """lm_head on the rows that are read (1 for plain decoding, 1 + W + g gs for a lookahead step): the skinny GEMM WITHOUT split-K -
         N / bn work-groups cover the CUs on their own at vocabulary sizes, the output is written once in the model dtype - against
         the library.  Measured at V = 32000, K = 4096, 16 rows: library 57.3 us, skinny on row-major weights 48.3 us, on the K-tile-major
-        copy 39.4 us (6.65 TB/s; `profiles/r3_lm_head_probe.txt`)."""
-        mbs = mclass // 32
-
-        def time_it(fn, reps=12):
-            best_t = float("inf")
-            for rnd in range(2):
-                fn()
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(reps):
-                    fn()
-                e1.record()
-                torch.cuda.synchronize()
-                best_t = min(best_t, e0.elapsed_time(e1) / reps)
-            return best_t
-
-        t_lib = time_it(lambda: torch.matmul(a, ws_lib[0].t(), out=out))
-        timed = []
-        for bn in (64, 96, 128, 192, 256):
-            for mt in sorted({1, mbs if mbs <= 5 else mbs // 2}):
-                for nt in (0, 1, 2):
-                    if mbs % mt:
-                        continue
-                    try:
-                        t = time_it(lambda: ops.gemm_skinny(a, ws[0], out=out, n_split=1, bn=bn, mb=mbs, mt=mt, nt=nt))
-                    except cabi.LadeHipError:
-                        continue                      # wave grid not built for this row class
-                    timed.append((t, (mbs, bn, 1, mt, nt, 0)))
+        copy 39.4 us (6.65 TB/s; `profiles/r3_lm_head_probe.txt`).  -> (winner, its ms, no ranking)"""
+        ms = lambda fn: time_launches(lambda _i: fn(), warmup=1, reps=12)
+        ms_of = lambda c: ms(lambda: c.gemm_skinny(a, ws[0], out))
+        t_lib = ms(lambda: torch.matmul(a, ws_lib[0].t(), out=out))
+        timed = _time_each(lm_head_candidates(mclass), ms_of)
         if cabi.debug("tune_ring", "0") != "0":
-            for t0, (mb, bn, S, mt, nt, _r) in sorted(timed)[:2]:
-                stage_bytes = (bn + 32 * mb) * 128
-                for ring in (3, 5, 6, 8):
-                    if ring * stage_bytes > 160 * 1024 or ring == min(4, 160 * 1024 // stage_bytes):
-                        continue
-                    try:
-                        t = time_it(lambda: ops.gemm_skinny(a, ws[0], out=out, n_split=1, bn=bn, mb=mb, mt=mt, nt=nt, ring=ring))
-                    except cabi.LadeHipError:
-                        continue
-                    timed.append((t, (mb, bn, 1, mt, nt, ring)))
-        best, t_best = None, t_lib
-        if timed and min(timed)[0] < t_lib:
-            t_best, best = min(timed)
-        self._tuned_ms = t_best
-        if cabi.debug("tune_verbose"):
-            top = " ".join(f"{c}:{t * 1e3:.1f}" for t, c in sorted(timed)[:4])
-            print(f"[tune] lm_head:{mclass} rows={a.shape[0]} N={N} K={K} lib {t_lib * 1e3:.1f} us | best {best} {t_best * 1e3:.1f} us "
-                  f"({N * K * 2 / 1e6 / (t_best * 1e3):.2f} TB/s) | {top}", file=sys.stderr, flush=True)
-        return best
+            timed += _time_each([r for _t, c in sorted(timed)[:2] for r in ring_variants(c, in_step=False)], ms_of)
+        return _winner(f"lm_head:{mclass} rows={a.shape[0]}", N, K, t_lib, timed, 4) + ([],)
 
     # ---- the same decisions, re-taken inside a step ------------------------------------------------------------------------
     STEP_TUNE_LAYERS = 8
@@ -418,23 +449,17 @@ class KernelDecisions:
         The probe step runs at a FIXED context (STEP_TUNE_CONTEXT keys, or the whole cache of a smaller engine - part of the cache key) on
         cache rows that are saved and restored, and on no live workspace; workspaces too small for the class's probe rows are grown first.
         One decision per model shape, row class, probe context and process; never taken during a stream capture (forward() refuses to
-        capture a class whose decision is still open: warm the class up first, or call prepare()).  LADE_TUNE_STEP=0 keeps the isolated table."""
-        if mclass in self._refined or self._refining or not self.custom_gemm:
-            return
+        capture a class whose decision is still open: warm the class up first, or call prepare()).  LADE_TUNE_STEP=0 keeps the isolated table.
+        Called by _decide alone, for an open class whose four isolated decisions it has just taken."""
         T = REP_ROWS[mclass]
-        esz = self.layers[0]["wo"].element_size() if "wo" in self.layers[0] else self.layers[0]["wo_kt"].element_size()
-        layer_bytes = esz * (self.hidden * ((self.H + 2 * self.Hkv) * self.d + self.H * self.d) + 3 * self.hidden * self.inter)
         n_probe = min(self.L, self.STEP_TUNE_LAYERS)
         if not self._step_tunable():
             self._refined.add(mclass)          # toy models sit in the Infinity Cache whatever runs: the isolated table stands (a property of the MODEL, not of this engine's buffers)
-            if self.tune_file:
-                self.save_tune_file()
+            self.save_tune_file()              # (a no-op without a tune file)
             return
         if torch.cuda.is_current_stream_capturing():
             raise cabi.LadeHipError(f"row class {mclass}: the in-step kernel decisions are still open during a stream capture - run the step eagerly once "
                                     f"(or StepEngine.prepare([rows])) before capturing it")
-        for n in self.LAYER_GEMMS:
-            self._tune(n, mclass)
         if T > self.max_T:
             # the probe wants REP_ROWS rows of workspace.  prepare() (construction time: nobody has captured a graph over the workspaces yet)
             # grows them, so that a decision does not depend on how this engine was sized; a LAZY refine from inside forward() / attn_choice()
@@ -457,13 +482,14 @@ class KernelDecisions:
                 self.attn_cfg[mclass] = tuple(c)
                 continue
             self.gemm_cfg[(n, mclass)] = c
-            ranked = dict((cfg[:5] if cfg else None, t) for t, cfg in reversed(self._ranked.get((n, mclass), [])))
-            if (n, mclass) in self.gemm_times:
-                self.gemm_times[(n, mclass)] = (ranked.get(c[:5] if c else None, self.gemm_times[(n, mclass)][0]), self.gemm_times[(n, mclass)][1])
+            if (n, mclass) in self.gemm_times:          # bench.py's report: the isolated time of the chosen SHAPE (whatever ring the step preferred)
+                shape = lambda cfg: cfg and cfg._replace(ring=0)
+                ranked = {shape(cfg): t for t, cfg in reversed(self._ranked.get((n, mclass), []))}
+                ms, nbytes = self.gemm_times[(n, mclass)]
+                self.gemm_times[(n, mclass)] = (ranked.get(shape(c), ms), nbytes)
         self.step_tune_log[mclass] = log
         self._refined.add(mclass)
-        if self.tune_file:
-            self.save_tune_file()
+        self.save_tune_file()
 
     def _step_tunable(self) -> bool:
         """whether this MODEL's decisions are re-taken inside a step: its first STEP_TUNE_LAYERS layers must outweigh the Infinity Cache"""
@@ -478,34 +504,22 @@ class KernelDecisions:
         """Takes every kernel decision a step of each of these row counts needs (isolated GEMM pass, the in-step pass, the attention launch
         parameters) NOW - at construction / before the first request - instead of inside the first live forward of each row class, which
         would stall that request for seconds (4 projections + the attention launch x up to 18 graph captures)."""
-        if not self.custom_gemm:
-            return
         with torch.cuda.device(self.device):
             for T in rows:
-                mclass = next((c for c in self.ROW_CLASSES if T <= c), None)
-                if mclass is None:
-                    continue
-                for n in self.LAYER_GEMMS:
-                    self._tune(n, mclass)
-                self._refine_in_step(mclass, allow_grow=True)
+                mclass = self.row_class(T)
+                if mclass is not None:
+                    self._decide(mclass, allow_grow=True)
 
     def _step_candidates(self, name: str, mclass: int):
-        ranked = [c for _t, c in self._ranked.get((name, mclass), [])]
-        inc = self.gemm_cfg[(name, mclass)]
-        shapes = [c for c in ranked[:3] if c is not None]
-        for S in sorted({c[2] for c in ranked if c is not None})[:2]:                   # the best candidate of the two smallest split counts
-            shapes.append(next(c for c in ranked if c is not None and c[2] == S))
-        out = [inc]
+        """what the in-step pass times for a projection: the incumbent, then the isolated pass's best three and its best of the two smallest
+        split counts, each at every ring depth"""
+        ranked = [c for _t, c in self._ranked.get((name, mclass), []) if c is not None]
+        shapes = [c for _t, c in self._ranked.get((name, mclass), [])[:3] if c is not None]
+        for S in sorted({c.n_split for c in ranked})[:2]:
+            shapes.append(next(c for c in ranked if c.n_split == S))
+        out = [self.gemm_cfg[(name, mclass)]]
         for c in shapes:
-            stage_bytes = (c[1] + 32 * c[0]) * 128
-            dflt = min(4, 160 * 1024 // stage_bytes)
-            # (the depths the kernel is compiled for: 2, 3, 4 = default, 5, 6, 8; a DOUBLE buffer only for the large stages of the 160-row
-            # class and wider: two stages beat three on 13B gate/up at 256 weight rows + 160 activation rows, 68.9 vs 71.7 us isolated, and
-            # the in-step pass picks them for all four projections of the 13B 192-row class, profiles/r6_rows_curve_13b.txt)
-            for ring in (0, 3, 5, 6, 8) + ((2,) if stage_bytes >= 32 * 1024 else ()):
-                cand = c[:5] + (ring,)
-                if (ring == 0 or (ring != dflt and ring * stage_bytes <= 160 * 1024)) and cand not in out:
-                    out.append(cand)
+            out += [cand for cand in ring_variants(c, in_step=True) if cand not in out]
         return out[:18]
 
     def _attn_candidates(self, mclass: int, T: int, S_tot: int):
@@ -644,9 +658,8 @@ class KernelDecisions:
         if not self.custom_gemm:
             return {}
         for m in self.ROW_CLASSES:
-            for n in self.GEMM_NAMES:
-                self._tune(n, m)
-            self._refine_in_step(m, allow_grow=True)
+            self._decide(m, allow_grow=True)
+            self._tune("lm_head", m)
         out = {f"{n}:{m}": self.gemm_cfg[(n, m)] for n in self.GEMM_NAMES for m in self.ROW_CLASSES}
         out.update({f"attn:{m}": tuple(self.attn_cfg.get(m, self.attn_default)) + (0, 0, 0) for m in self.ROW_CLASSES})
         return out
@@ -658,5 +671,5 @@ class KernelDecisions:
                 if v is not None:
                     self.attn_cfg[int(m)] = tuple(int(x) for x in v[:3])
                 continue
-            self.gemm_cfg[(n, int(m))] = None if v is None else (tuple(v) + (0,))[:6]       # (a 5-tuple of an older table: default ring)
+            self.gemm_cfg[(n, int(m))] = None if v is None else GemmCfg(*tuple(v)[:6])       # (a 5-tuple of an older table: default ring)
             self._refined.add(int(m))                # an adopted decision is final: every replica must run the kernels rank 0 chose

@@ -15,11 +15,9 @@ def _cfg():
 
 def _fresh_process_state():
     """what a new process starts with: no in-process decision caches"""
-    from lookaheaddecoding_amd import engine
-    engine._TUNE_CACHE.clear()
-    engine._TUNE_TIMES.clear()
-    engine._TUNE_RANKED.clear()
-    engine._STEP_TUNE_CACHE.clear()
+    from lookaheaddecoding_amd import tuning
+    tuning._TUNE_CACHE.clear()
+    tuning._STEP_TUNE_CACHE.clear()
 
 
 def _step(eng, T=60, P=60, seed=5):
@@ -58,10 +56,10 @@ def test_tune_file_is_written_adopted_by_a_differently_sized_engine_and_refused_
     b = StepEngine(cfg, w, dtype=torch.bfloat16, max_seq=4096, max_T=512)
     assert sorted(b.tune_loaded) == [64] and 64 in b._refined
     assert all(b.gemm_cfg[(n, 64)] == a.gemm_cfg[(n, 64)] for n in b.LAYER_GEMMS) and b.gemm_cfg[("lm_head", 32)] == a.gemm_cfg[("lm_head", 32)]
-    from lookaheaddecoding_amd import engine
-    assert not engine._TUNE_CACHE and not engine._STEP_TUNE_CACHE          # nothing was measured
+    from lookaheaddecoding_amd import tuning
+    assert not tuning._TUNE_CACHE and not tuning._STEP_TUNE_CACHE          # nothing was measured
     assert torch.equal(_step(b), logits_a)
-    assert not [k for k in engine._TUNE_CACHE if k[2] == 64]                 # ... not by the step either
+    assert not [k for k in tuning._TUNE_CACHE if k[2] == 64]                 # ... not by the step either
 
     # the file decides, not the box: an edited decision is what the next engine launches
     forced = [2, 64, 2, 1, 1, 0]
@@ -81,3 +79,27 @@ def test_tune_file_is_written_adopted_by_a_differently_sized_engine_and_refused_
     path.write_text(json.dumps(doc))
     with pytest.raises(cabi.LadeHipError, match="refusing to adopt"):
         StepEngine(cfg, w, dtype=torch.bfloat16, max_seq=1024, max_T=256)
+
+
+def test_prepare_a_first_forward_and_attn_choice_decide_a_row_class_alike(monkeypatch):
+    """The three lazy ways into the one gate (KernelDecisions._decide) on a model BELOW the in-step threshold, where the gate's isolated pass is
+    all that is taken: each leaves the class closed with a GemmCfg (or the library) per layer projection, the same ones (one decision per shape
+    and process), and a step whose first forward had to decide computes what a prepared engine's step computes - its tuning pass, which
+    scribbles over ws_part, ran before the step wrote anything."""
+    from lookaheaddecoding_amd.engine import StepEngine
+    from lookaheaddecoding_amd.tuning import GemmCfg
+    from lookaheaddecoding_amd.weights import random_weights_torch
+    monkeypatch.setenv("LADE_TUNE_FILE", "off")
+    cfg = _cfg()
+    w = random_weights_torch(cfg, seed=3, dtype=torch.bfloat16)
+    _fresh_process_state()
+    by_forward, by_prepare, by_attn_choice = (StepEngine(cfg, w, dtype=torch.bfloat16, max_seq=2560, max_T=256) for _ in range(3))
+    assert not by_forward._step_tunable() and not by_forward.tune_loaded
+    logits_forward = _step(by_forward)                   # its first forward (60 rows, eager) finds the class open: this one measures
+    by_prepare.prepare([60])
+    assert by_attn_choice.attn_choice(60) == (0, 128, 0)
+    for e in (by_forward, by_prepare, by_attn_choice):
+        assert 64 in e._refined
+        assert all(type(e.gemm_cfg[(n, 64)]) in (GemmCfg, type(None)) for n in e.LAYER_GEMMS)
+        assert [e.gemm_cfg[(n, 64)] for n in e.LAYER_GEMMS] == [by_forward.gemm_cfg[(n, 64)] for n in e.LAYER_GEMMS]
+    assert torch.equal(_step(by_prepare), logits_forward)

@@ -12,6 +12,7 @@ os.environ["LADE_TUNE_FILE"] = out
 import torch
 
 from lookaheaddecoding_amd.engine import StepEngine
+from lookaheaddecoding_amd.tuning import shipped_tune_table
 from lookaheaddecoding_amd.weights import make_config, random_weights_torch
 
 NAMES = {"7b": "llama2-7b", "13b": "codellama-13b", "70b": "llama2-70b"}
@@ -31,4 +32,4 @@ for spec in sys.argv[2:]:
         print("   ", m, {n: table.get(f"{n}:{m}") for n in eng.GEMM_NAMES}, flush=True)
     del eng
     torch.cuda.empty_cache()
-print("device:", torch.cuda.get_device_name(0), "->", os.path.basename(__import__("lookaheaddecoding_amd.engine", fromlist=["x"]).shipped_tune_table(torch.device("cuda", 0))))
+print("device:", torch.cuda.get_device_name(0), "->", os.path.basename(shipped_tune_table(torch.device("cuda", 0))))

@@ -49,6 +49,6 @@ for T in ROWS:
         best = min(best, e0.elapsed_time(e1) / 4)
     if t1 is None:
         t1 = best
-    cls = next((c for c in eng.ROW_CLASSES if T <= c), None)
+    cls = eng.row_class(T)
     cfgs = " ".join(f"{n}={eng.gemm_cfg.get((n, cls))}" for n in eng.LAYER_GEMMS)
     print(f"  T={T:4d}  {best:7.3f} ms  x{best / t1:5.3f} of the first row count  class {cls}  {cfgs}", flush=True)
