@@ -41,6 +41,8 @@
  *                            finally drawn from) / the per-candidate draft probabilities of the acceptance loop, gathered on
  *                            the device without materialising guess_probs   lade/decoding.py:484-540
  *   lade_warp_rows           temperature / top-k / top-p warpers in one launch   lade/decoding.py:375-377, :443, :488
+ *   lade_warp_rows_ex        the same launch followed by HF's min-p, typical, epsilon and eta warpers (transformers
+ *                            generation/logits_process.py; the reference refuses every warper beyond the three, lade/decoding.py:375-377)
  *   lade_rmsnorm / lade_embed_rmsnorm / lade_add_rmsnorm / lade_silu_mul / lade_gather_rows   LlamaRMSNorm (+ residual add), SwiGLU,
  *                            embedding / logits-row gather around the GEMMs
  *                            lade/models/modeling_llama.py:222-227, :360-380, :1164 ("next" row)
@@ -442,6 +444,30 @@ int lade_softmax_gather(const void* logits, int64_t ld, int32_t rows, int32_t V,
  * (same results; 0.4 ms for 31 rows of 128256 against 0.8 ms of torch topk / sort).  V <= 2^24. */
 int lade_warp_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t dtype, float temperature, int32_t top_k,
                    float top_p, int32_t skip, float* out, void* stream);
+/* The same launch with the rest of the truncation warpers generate() builds behind top-p (transformers generation/utils.py
+ * _get_logits_processor: MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper, EtaLogitsWarper of generation/logits_process.py, in
+ * that order; the reference refuses them, lade/decoding.py:375-377).  Each stage acts on the survivors of the one before, with masses
+ * E = round(exp(x - max) * 2^40), Z = sum E and entropy H = log(Z / 2^40) + sum E (max - x) / Z all in 64-bit fixed point, so no cut depends
+ * on the order of a summation and both kernel forms place the same ones:
+ *   min_p            remove p < min_p * p_max                                  (E < min_p * 2^40; 0 = off)
+ *   typical_p        keep the tokens whose |-log p - H| (fp32) is at most D, the smallest distance with mass(d <= D) >= typical_p; a tie
+ *                    group in d stays or goes whole; the largest token may go      (>= 1 = off)
+ *   epsilon_cutoff   remove p < epsilon unless x equals the maximum              (0 = off)
+ *   eta_cutoff       the same with eta = min(epsilon, sqrt(epsilon) * exp(-H))   (0 = off)
+ * (filter_value = -inf and min_tokens_to_keep = 1 of the HF classes.)  With all four off this is lade_warp_rows: the same kernels.  With one
+ * of them on, the output-row form of the kernel runs at every V (the register form has no registers left for the stages).
+ * LADE_E_ARG, before any launch, for params == NULL, min_p outside [0, 1], typical_p outside (0, 1], a cutoff outside [0, 1). */
+typedef struct lade_warp_params {
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    float min_p;
+    float typical_p;
+    float epsilon_cutoff;
+    float eta_cutoff;
+} lade_warp_params;
+int lade_warp_rows_ex(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t dtype, const lade_warp_params* params, int32_t skip,
+                      float* out, void* stream);
 
 /* ---- glue around the GEMMs -------------------------------------------------------------- */
 /* y = weight * (x * rsqrt(mean(x^2) + eps)) with the reference's rounding (fp32 norm, cast, then * weight) */

@@ -67,6 +67,12 @@ class QkvEpilogue(C.Structure):
     _fields_ = [("bias", C.c_void_p), ("q_norm", C.c_void_p), ("k_norm", C.c_void_p), ("eps", C.c_float)]
 
 
+class WarpParams(C.Structure):
+    """lade_warp_params: the seven warper settings of lade_warp_rows_ex, in HF's order of application"""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float), ("typical_p", C.c_float),
+                ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float)]
+
+
 _lib: Optional[C.CDLL] = None
 
 _i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -112,6 +118,7 @@ SIGNATURES = {
     "lade_softmax_rows": [_vp, _i64, _i32, _i32, _i32, _f32, _vp, _vp],
     "lade_softmax_gather": [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "lade_warp_rows": [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _vp],
+    "lade_warp_rows_ex": [_vp, _i64, _i32, _i32, _i32, C.POINTER(WarpParams), _i32, _vp, _vp],
     "lade_rmsnorm": [_vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
     "lade_embed_rmsnorm": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
     "lade_add_rmsnorm": [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp],

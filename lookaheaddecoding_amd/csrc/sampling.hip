@@ -13,6 +13,19 @@
 // The cumulative mass is accumulated in 64-bit FIXED POINT (exp(x - max) * 2^40): integer sums do not depend on the order of
 // summation, so the cut is deterministic; against torch's fp32 cumsum (whose own order is unspecified) it can only differ when the
 // mass at a token falls within ~1e-7 of the cut.
+//
+// lade_warp_rows_ex: the four truncation warpers HF's generate() builds behind top-p (MinPLogitsWarper, TypicalLogitsWarper,
+// EpsilonLogitsWarper, EtaLogitsWarper of transformers' generation/logits_process.py, filter_value = -inf, min_tokens_to_keep = 1), in its
+// order, each on the survivors of the stage before, the maximum mx taken anew (typical may remove the largest token):
+//   min_p           remove E < min_p * 2^40                               (p < min_p * p_max: the largest survivor has E = 2^40)
+//   typical_p       d = |-log p - H| in fp32; keep d <= D, D the smallest distance with mass(d <= D) >= typical_p * Z - the nucleus search over
+//                   another key with < for <=; kept by value, so a tie group in d stays or goes whole
+//   epsilon_cutoff  remove E < epsilon * Z unless x = mx                   (ties with the maximum stay)
+//   eta_cutoff      the same with eta = min(epsilon, sqrt(epsilon) * exp(-H))
+// with E = round(exp(x - mx) * 2^40), Z = sum E and the entropy H = log(Z / 2^40) + sum round(E * (mx - x)) / Z, all sums in 64-bit fixed point:
+// no cut depends on the order of a summation.  The stages are a template flag of the output-row kernel (its instances that take a WarpEx), which then runs at every V: the
+// register kernel sits at the 128 VGPRs its 1024 threads allow and every form of the stages tried in it went to scratch.  Without
+// a later stage both entry points launch the kernels without the flag: the code and the bits they have always had.
 #include <stdlib.h>
 
 #include "common.hpp"
@@ -62,6 +75,39 @@ __device__ __forceinline__ U wg_max(U v, U* red, int& turn) {
 #pragma unroll
     for (int w = 1; w < WARP_WAVES; ++w) t = r[w] > t ? r[w] : t;
     return t;
+}
+
+// ---- the cut-offs behind top-p (min_p, typical_p, epsilon_cutoff, eta_cutoff: the WarpEx instances of the output-row kernel) ---------------------
+// Every quantity is an integer or a function of integers: E = fixed-point mass of a surviving key, Z = sum E, S = sum round(E * (mx - x)) -
+// the row's entropy is H = log(Z / 2^40) + S / Z, and since -log p = (mx - x) + log(Z / 2^40), typical decoding's distance |-log p - H| is
+// |(mx - x) - S / Z|: no logarithm is ever taken, and no sum depends on the order it was taken in.
+struct WarpEx { float min_p, typical_p, epsilon, eta; };
+constexpr double FX_ONE = 1099511627776.0;           // 2^40
+
+__device__ __forceinline__ unsigned long long fx_mass(uint32_t k, float mx) {                     // 0 for a removed or padding key
+    const float ev = k > 0x007fffffu ? __expf(key_float(k) - mx) : 0.f;
+    return (unsigned long long)((double)ev * FX_ONE + 0.5);
+}
+__device__ __forceinline__ unsigned long long fx_surprisal(uint32_t k, float mx, unsigned long long E) {      // <= 2^40 / e: 2^24 of them fit 64 bits
+    const float delta = k > 0x007fffffu ? mx - key_float(k) : 0.f;
+    return (unsigned long long)((double)E * (double)delta + 0.5);
+}
+__device__ __forceinline__ float fx_mean_surprisal(unsigned long long S, unsigned long long Z) { return (float)((double)S / (double)Z); }
+__device__ __forceinline__ uint32_t typical_key(uint32_t k, float mx, float A) {                  // bit pattern of a non-negative float: ordered as the float
+    return __float_as_uint(fabsf((mx - key_float(k)) - A));
+}
+// smallest integer a mass must reach to count as >= f * Z (masses are integers: E < f * Z  <=>  E < fx_ceil(f * Z))
+__device__ __forceinline__ unsigned long long fx_ceil(double v) { return (unsigned long long)ceil(v); }
+__device__ __forceinline__ unsigned long long min_p_bound(float min_p) { return fx_ceil((double)min_p * FX_ONE); }       // the largest survivor has E = 2^40
+__device__ __forceinline__ unsigned long long typical_bound(float m, unsigned long long Z) {
+    const unsigned long long t = fx_ceil((double)m * (double)Z);
+    return t < 1ull ? 1ull : (t > Z ? Z : t);
+}
+__device__ __forceinline__ unsigned long long epsilon_bound(float eps, unsigned long long Z) { return fx_ceil((double)eps * (double)Z); }
+// eta = min(eps, sqrt(eps) * exp(-H)) with sqrt in fp32 as HF takes it (its epsilon is an fp32 tensor); exp(-H) * Z = 2^40 * exp(-S / Z)
+__device__ __forceinline__ unsigned long long eta_bound(float eps, unsigned long long S, unsigned long long Z) {
+    const double a = (double)eps * (double)Z, b = (double)__fsqrt_rn(eps) * FX_ONE * exp(-((double)S / (double)Z));
+    return fx_ceil(b < a ? b : a);
 }
 
 template <typename T>
@@ -204,9 +250,11 @@ __device__ __forceinline__ void wg_sum_vec(U (&v)[BIG_M], U* red, int& turn) {  
     }
 }
 
-template <typename T>
+// (Ex: empty, or one WarpEx - the instance with the later stages; the one without them keeps the argument list it has always had)
+template <typename T, typename... Ex>
 __global__ __launch_bounds__(WARP_THREADS) void warp_rows_big_kernel(const void* logits, int64_t ld, int V, float temperature, int top_k, float top_p,
-                                                                     int skip, float* out) {
+                                                                     int skip, float* out, Ex... later) {
+    constexpr bool EX = sizeof...(Ex) > 0;
     __shared__ unsigned long long red64[2 * WARP_WAVES];
     __shared__ uint32_t red32[2 * WARP_WAVES];
     __shared__ unsigned long long red64v[2 * WARP_WAVES * BIG_M];
@@ -373,7 +421,8 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_rows_big_kernel(const void*
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 if (nucleus && k[e] < K) k[e] = KEY_NEG_INF;
-                o4[e] = key_float(k[e] == 0u ? KEY_NEG_INF : k[e]);
+                if constexpr (EX) o4[e] = __uint_as_float(k[e]);      // the row stays in keys for the stages below (removed: the key of -inf)
+                else o4[e] = key_float(k[e] == 0u ? KEY_NEG_INF : k[e]);
             }
             float* o = reinterpret_cast<float*>(kb) + 4 * (size_t)q;
             if (vec) *reinterpret_cast<float4*>(o) = float4{o4[0], o4[1], o4[2], o4[3]};
@@ -383,29 +432,146 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_rows_big_kernel(const void*
                     if (4 * q + e < V) o[e] = o4[e];
         }
     }
+
+    // ---- min_p -> typical_p -> epsilon_cutoff -> eta_cutoff on the keys in the output row, then keys -> values ----
+    if constexpr (EX) {
+        const WarpEx ex = (later, ...);
+        // a thread rewrites its own groups (the groups `walk` hands it): f maps a key to its successor
+        auto rewrite = [&](auto&& f) {
+            for (int q0 = tid; q0 < NQ; q0 += UNR * WARP_THREADS) {
+                uint4 kk[UNR];
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) {
+                    const int q = q0 + u * WARP_THREADS;
+                    kk[u] = q < NQ ? load4(q) : uint4{0u, 0u, 0u, 0u};
+                }
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) {
+                    const int q = q0 + u * WARP_THREADS;
+                    if (q >= NQ) continue;
+                    const uint4 r = uint4{f(kk[u].x), f(kk[u].y), f(kk[u].z), f(kk[u].w)};
+                    uint32_t* o = kb + 4 * (size_t)q;
+                    if (vec) *reinterpret_cast<uint4*>(o) = r;
+                    else {
+                        o[0] = r.x;
+                        if (4 * q + 1 < V) o[1] = r.y;
+                        if (4 * q + 2 < V) o[2] = r.z;
+                        if (4 * q + 3 < V) o[3] = r.w;
+                    }
+                }
+            }
+        };
+        if (!nucleus) kmax = wg_max<uint32_t>(kmax, red32, t32);      // (neither top-k nor top-p removes the largest key)
+        float mx = key_float(kmax);
+        unsigned long long Z = 0, S = 0;
+        auto sums = [&](bool entropy) {                // Z, and S where the stage needs the entropy, over the survivors
+            unsigned long long z = 0, s = 0;
+            walk([&](uint32_t k) {
+                if (k > KEY_NEG_INF) {
+                    const unsigned long long ms = fx_mass(k, mx);
+                    z += ms;
+                    if (entropy) s += fx_surprisal(k, mx, ms);
+                }
+            });
+            Z = wg_sum<unsigned long long>(z, red64, t64);
+            if (entropy) S = wg_sum<unsigned long long>(s, red64, t64);
+        };
+        auto drop_light = [&](unsigned long long bound) {        // mass below the bound and not the maximum (ties with it stay)
+            rewrite([&](uint32_t k) { return (k > KEY_NEG_INF && k < kmax && fx_mass(k, mx) < bound) ? KEY_NEG_INF : k; });
+        };
+        if (ex.min_p > 0.f) drop_light(min_p_bound(ex.min_p));
+        if (ex.typical_p < 1.0f) {
+            sums(true);
+            const float A = fx_mean_surprisal(S, Z);
+            const unsigned long long M = typical_bound(ex.typical_p, Z);
+            // D = largest distance key with mass(d < D) < M, BIG_BITS bits per pass (the nucleus search above over another key)
+            uint32_t D = 0;
+            unsigned long long below_D = 0;
+            for (int b = 32 - BIG_BITS; b >= 0; b -= BIG_BITS) {
+                unsigned long long mlt[BIG_M];             // mlt[m] = mass of the distances in [D, D | (m+1) << b)
+#pragma unroll
+                for (int m = 0; m < BIG_M; ++m) mlt[m] = 0ull;
+                const uint32_t hi = D | ((uint32_t)BIG_M << b);
+                walk([&](uint32_t k) {
+                    if (k > KEY_NEG_INF) {
+                        const uint32_t dk = typical_key(k, mx, A);
+                        if (dk >= D && dk < hi) {
+                            const unsigned long long ms = fx_mass(k, mx);
+#pragma unroll
+                            for (int m = 0; m < BIG_M; ++m)
+                                if (dk < (D | ((uint32_t)(m + 1) << b))) mlt[m] += ms;
+                        }
+                    }
+                });
+                wg_sum_vec<unsigned long long>(mlt, red64v, t64v);
+                uint32_t best = 0;
+#pragma unroll
+                for (int m = 0; m < BIG_M; ++m)
+                    if (below_D + mlt[m] < M) best = (uint32_t)(m + 1);
+                if (best) below_D += mlt[best - 1];
+                D |= best << b;
+            }
+            rewrite([&](uint32_t k) { return (k > KEY_NEG_INF && typical_key(k, mx, A) > D) ? KEY_NEG_INF : k; });
+            uint32_t km = 0;                           // the largest token may be gone
+            walk([&](uint32_t k) { km = k > km ? k : km; });
+            kmax = wg_max<uint32_t>(km, red32, t32);
+            mx = key_float(kmax);
+        }
+        if (ex.epsilon > 0.f) {
+            sums(false);
+            drop_light(epsilon_bound(ex.epsilon, Z));
+        }
+        if (ex.eta > 0.f) {
+            sums(true);
+            drop_light(eta_bound(ex.eta, S, Z));
+        }
+        rewrite([&](uint32_t k) { return __float_as_uint(key_float(k)); });
+    }
 }
 
 }  // namespace lade
 
 using namespace lade;
 
-extern "C" int lade_warp_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t dtype, float temperature, int32_t top_k,
-                              float top_p, int32_t skip, float* out, void* stream) {
-    LADE_REQUIRE(logits && out && rows >= 0 && V > 0 && ld >= V && temperature > 0.f && top_k >= 0 && top_p > 0.f && skip >= 0, LADE_E_ARG,
-                 "lade_warp_rows: rows=%d V=%d T=%f top_k=%d top_p=%f skip=%d", rows, V, temperature, top_k, top_p, skip);
-    LADE_REQUIRE(V <= (1 << 24), LADE_E_LIMIT, "lade_warp_rows: V=%d > %d", V, 1 << 24);
+template <typename T>
+static void launch_warp_rows(const void* logits, int64_t ld, int rows, int V, const lade_warp_params& p, int skip, float* out, hipStream_t st) {
+    const WarpEx ex{p.min_p, p.typical_p, p.epsilon_cutoff, p.eta_cutoff};
+    const dim3 grid(rows), block(WARP_THREADS);
+    // with none of the four later stages active the kernels are the ones without them: the same code and the same bits as before they existed
+    if (p.min_p > 0.f || p.typical_p < 1.f || p.epsilon_cutoff > 0.f || p.eta_cutoff > 0.f)      // the output-row form at every V (see its header)
+        hipLaunchKernelGGL((warp_rows_big_kernel<T, WarpEx>), grid, block, 0, st, logits, ld, V, p.temperature, p.top_k, p.top_p, skip, out, ex);
+    else if (V > WARP_THREADS * WARP_EPT)               // the row does not fit one work-group's registers: keys in the output row
+        hipLaunchKernelGGL(warp_rows_big_kernel<T>, grid, block, 0, st, logits, ld, V, p.temperature, p.top_k, p.top_p, skip, out);
+    else
+        hipLaunchKernelGGL(warp_rows_kernel<T>, grid, block, 0, st, logits, ld, V, p.temperature, p.top_k, p.top_p, skip, out);
+}
+
+static int warp_rows_checked(const char* who, const void* logits, int64_t ld, int rows, int V, int dtype, const lade_warp_params& p, int skip, float* out,
+                             void* stream) {
+    LADE_REQUIRE(logits && out && rows >= 0 && V > 0 && ld >= V && p.temperature > 0.f && p.top_k >= 0 && p.top_p > 0.f && skip >= 0, LADE_E_ARG,
+                 "%s: rows=%d V=%d T=%f top_k=%d top_p=%f skip=%d", who, rows, V, p.temperature, p.top_k, p.top_p, skip);
+    LADE_REQUIRE(p.min_p >= 0.f && p.min_p <= 1.f && p.typical_p > 0.f && p.typical_p <= 1.f && p.epsilon_cutoff >= 0.f && p.epsilon_cutoff < 1.f &&
+                     p.eta_cutoff >= 0.f && p.eta_cutoff < 1.f,
+                 LADE_E_ARG, "%s: min_p=%f (0..1) typical_p=%f (0 < .. <= 1) epsilon_cutoff=%f eta_cutoff=%f (0 <= .. < 1)", who, p.min_p, p.typical_p,
+                 p.epsilon_cutoff, p.eta_cutoff);
+    LADE_REQUIRE(V <= (1 << 24), LADE_E_LIMIT, "%s: V=%d > %d", who, V, 1 << 24);
     if (rows == 0) return LADE_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (V > WARP_THREADS * WARP_EPT) {                  // the row does not fit one work-group's registers: keys in the output row
-        if (dtype == LADE_F32) hipLaunchKernelGGL(warp_rows_big_kernel<F32>, dim3(rows), dim3(WARP_THREADS), 0, st, logits, ld, V, temperature, top_k, top_p, skip, out);
-        else if (dtype == LADE_BF16) hipLaunchKernelGGL(warp_rows_big_kernel<BF16>, dim3(rows), dim3(WARP_THREADS), 0, st, logits, ld, V, temperature, top_k, top_p, skip, out);
-        else if (dtype == LADE_F16) hipLaunchKernelGGL(warp_rows_big_kernel<F16>, dim3(rows), dim3(WARP_THREADS), 0, st, logits, ld, V, temperature, top_k, top_p, skip, out);
-        else LADE_REQUIRE(false, LADE_E_DTYPE, "lade_warp_rows: dtype=%d", dtype);
-        return check_launch("lade_warp_rows");
-    }
-    if (dtype == LADE_F32) hipLaunchKernelGGL(warp_rows_kernel<F32>, dim3(rows), dim3(WARP_THREADS), 0, st, logits, ld, V, temperature, top_k, top_p, skip, out);
-    else if (dtype == LADE_BF16) hipLaunchKernelGGL(warp_rows_kernel<BF16>, dim3(rows), dim3(WARP_THREADS), 0, st, logits, ld, V, temperature, top_k, top_p, skip, out);
-    else if (dtype == LADE_F16) hipLaunchKernelGGL(warp_rows_kernel<F16>, dim3(rows), dim3(WARP_THREADS), 0, st, logits, ld, V, temperature, top_k, top_p, skip, out);
-    else LADE_REQUIRE(false, LADE_E_DTYPE, "lade_warp_rows: dtype=%d", dtype);
-    return check_launch("lade_warp_rows");
+    if (dtype == LADE_F32) launch_warp_rows<F32>(logits, ld, rows, V, p, skip, out, st);
+    else if (dtype == LADE_BF16) launch_warp_rows<BF16>(logits, ld, rows, V, p, skip, out, st);
+    else if (dtype == LADE_F16) launch_warp_rows<F16>(logits, ld, rows, V, p, skip, out, st);
+    else LADE_REQUIRE(false, LADE_E_DTYPE, "%s: dtype=%d", who, dtype);
+    return check_launch(who);
+}
+
+extern "C" int lade_warp_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t dtype, float temperature, int32_t top_k,
+                              float top_p, int32_t skip, float* out, void* stream) {
+    const lade_warp_params p{temperature, top_k, top_p, 0.f, 1.f, 0.f, 0.f};
+    return warp_rows_checked("lade_warp_rows", logits, ld, rows, V, dtype, p, skip, out, stream);
+}
+
+extern "C" int lade_warp_rows_ex(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t dtype, const lade_warp_params* params, int32_t skip,
+                                 float* out, void* stream) {
+    LADE_REQUIRE(params, LADE_E_ARG, "lade_warp_rows_ex: null params");
+    return warp_rows_checked("lade_warp_rows_ex", logits, ld, rows, V, dtype, *params, skip, out, stream);
 }

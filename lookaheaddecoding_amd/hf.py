@@ -258,14 +258,29 @@ def _criteria_limits(stopping_criteria, generation_config=None):
     return max_length, eos
 
 
+def admitted_warpers():
+    """The warper classes a sampling generate() may carry under lookahead, in the order HF's generate() builds them: the three the
+    reference admits (lade/decoding.py:375-377) and the four truncation warpers behind them (transformers generation/utils.py,
+    _get_logits_processor)."""
+    from transformers.generation import logits_process as lp
+    return (lp.TemperatureLogitsWarper, lp.TopKLogitsWarper, lp.TopPLogitsWarper, lp.MinPLogitsWarper, lp.TypicalLogitsWarper,
+            lp.EpsilonLogitsWarper, lp.EtaLogitsWarper)
+
+
+def _check_admitted(warpers):
+    kinds = admitted_warpers()
+    for wp in warpers:
+        assert type(wp) in kinds, f"please set top_k=0.0 and top_p=1.0 {wp}"
+
+
 def controls_from_processors(processors):
     """Splits HF's logits-processor list into what the device step applies and the rest: (GenControls or None, remaining).
     Taken: RepetitionPenaltyLogitsProcessor (without prompt_ignore_length), MinLengthLogitsProcessor, MinNewTokensLengthLogitsProcessor.
-    Everything else stays in `remaining` (the temperature / top-k / top-p warpers of a sampling call, or a processor the callers refuse
-    as before).  HF applies processors before warpers; a taken processor placed after a warper is refused (AssertionError), since the
+    Everything else stays in `remaining` (the warpers of a sampling call, `admitted_warpers`, or a processor the callers refuse as
+    before).  HF applies processors before warpers; a taken processor placed after a warper is refused (AssertionError), since the
     device step applies the controls to the raw logits."""
     from transformers.generation import logits_process as lp
-    warper_kinds = (lp.TemperatureLogitsWarper, lp.TopKLogitsWarper, lp.TopPLogitsWarper)
+    warper_kinds = admitted_warpers()
     penalty, min_len, mask_eos, rest = 1.0, 0, None, []
     for p in (processors or []):
         kind = type(p)
@@ -404,48 +419,60 @@ def jacobi_greedy_search_multilevel(self, input_ids, logits_processor=None, stop
     return _run(self, input_ids, False, None, stopping_criteria, eos_token_id, generation_config, streamer, chat, controls, request)
 
 
-def _canonical_warper(warpers, T_cls, K_cls, P_cls):
-    """(temperature, top_k, top_p) when the list is what `generate()` builds - at most one warper of each kind, in the order
-    temperature, top-k, top-p, filtering with -inf and keeping one token - else None (the list is then applied as given)."""
-    order = {T_cls: 0, K_cls: 1, P_cls: 2}
-    kinds = [order[type(wp)] for wp in warpers]
-    if kinds != sorted(set(kinds)):
+def _canonical_warper(warpers):
+    """The seven parameters (temperature, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff) when the list is what `generate()`
+    builds - at most one warper of each admitted kind, in HF's order, filtering with -inf and keeping one token - else None (the list
+    is then applied as given)."""
+    lp_T, lp_K, lp_P, lp_min_p, lp_typical, lp_epsilon, lp_eta = kinds_in_order = admitted_warpers()
+    order = {cls: i for i, cls in enumerate(kinds_in_order)}
+    kinds = [order.get(type(wp)) for wp in warpers]
+    if None in kinds or kinds != sorted(set(kinds)):       # (a kind that is not admitted: the callers have refused it before; never canonical)
         return None
-    t, k, p = 1.0, 0, 1.0
+    t, k, p, min_p, typical_p, epsilon_cutoff, eta_cutoff = 1.0, 0, 1.0, 0.0, 1.0, 0.0, 0.0
     for wp in warpers:
-        if type(wp) is T_cls:
+        kind = type(wp)
+        if kind is lp_T:
             t = float(wp.temperature)
+            continue
+        if getattr(wp, "filter_value", -float("inf")) != -float("inf") or getattr(wp, "min_tokens_to_keep", 1) != 1:
+            return None
+        if kind is lp_K:
+            k = int(wp.top_k)
+        elif kind is lp_P:
+            p = float(wp.top_p)
+        elif kind is lp_min_p:
+            min_p = float(wp.min_p)
+        elif kind is lp_typical:
+            typical_p = float(wp.mass)
+        elif kind is lp_epsilon:
+            epsilon_cutoff = float(wp.epsilon)
         else:
-            if getattr(wp, "filter_value", -float("inf")) != -float("inf") or getattr(wp, "min_tokens_to_keep", 1) != 1:
-                return None
-            if type(wp) is K_cls:
-                k = int(wp.top_k)
-            else:
-                p = float(wp.top_p)
-    return t, k, p
+            eta_cutoff = float(wp.epsilon)                 # (EtaLogitsWarper keeps it as an fp32 tensor)
+    return t, k, p, min_p, typical_p, epsilon_cutoff, eta_cutoff
 
 
 def jacobi_sample_multilevel(self, input_ids, logits_processor=None, stopping_criteria=None, logits_warper=None, max_length=None,
                              pad_token_id=None, eos_token_id=None, output_attentions=None, output_hidden_states=None, output_scores=None,
                              return_dict_in_generate=None, synced_gpus=False, streamer=None, chat=False, generation_config=None,
                              controls=None, output_logits=None, **model_kwargs):
-    """Same call contract as lade/decoding.py:137-154.  Warpers are restricted like the reference (:375-377); repetition penalty and
+    """Same call contract as lade/decoding.py:137-154.  Warpers are restricted to `admitted_warpers` (the reference's three, :375-377, and HF's
+    min-p / typical / epsilon / eta behind them); repetition penalty and
     min length among the logits processors run on the device (`controls`: already split off by _sample_proxy).  With
     return_dict_in_generate: GenerateDecoderOnlyOutput, `scores` = the warped rows (the reference asserts that off at the head of its loop)."""
     request = output_request(generation_config, return_dict_in_generate, output_scores, output_logits, output_attentions, output_hidden_states)
     if controls is None:
         controls, _ = controls_from_processors(logits_processor)
-    from transformers.generation.logits_process import TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper
     warpers = list(logits_warper or [])
-    for wp in warpers:
-        assert type(wp) in (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper), f"please set top_k=0.0 and top_p=1.0 {wp}"
+    _check_admitted(warpers)
 
     from .sampling import Warper
-    canonical = _canonical_warper(warpers, TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper)
+    canonical = _canonical_warper(warpers)
     if canonical is not None:
-        # HF's own construction order (temperature -> top-k -> top-p, -inf filter, one token kept): the device kernels apply it -
-        # temperature alone inside the probability kernels (BASELINE config 3), with top-k / top-p as one lade_warp_rows launch
-        warp = Warper(*canonical)
+        # HF's own construction order (temperature -> top-k -> top-p -> min-p -> typical -> epsilon -> eta, -inf filter, one token kept): the
+        # device kernels apply it - temperature alone inside the probability kernels (BASELINE config 3), anything more as one
+        # lade_warp_rows / lade_warp_rows_ex launch
+        t, k, p, min_p, typical_p, epsilon_cutoff, eta_cutoff = canonical
+        warp = Warper(t, k, p, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
     else:
         def warp(scores):
             for wp in warpers:
@@ -483,10 +510,8 @@ def _sample_proxy(self, input_ids, logits_processor=None, stopping_criteria=None
     chat = bool(int(os.environ.get("CHAT", 0)))
     output_request(generation_config)            # (refuses attentions / hidden states before any work; the two loops read the flags themselves)
     if generation_config.do_sample:
-        from transformers.generation.logits_process import TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper
         controls, warpers = controls_from_processors(logits_processor)      # processors first, then the warpers (HF's order)
-        for wp in warpers:
-            assert type(wp) in (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper), f"please set top_k=0.0 and top_p=1.0 {wp}"
+        _check_admitted(warpers)
         return jacobi_sample_multilevel(self, input_ids, stopping_criteria=stopping_criteria, logits_warper=warpers, streamer=streamer,
                                         chat=chat, generation_config=generation_config, controls=controls)
     return jacobi_greedy_search_multilevel(self, input_ids, logits_processor=logits_processor, stopping_criteria=stopping_criteria,

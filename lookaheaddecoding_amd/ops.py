@@ -316,11 +316,8 @@ def softmax_rows(logits: torch.Tensor, temperature: float = 1.0, out: Optional[t
 WARP_MAX_V = 1 << 24      # lade_warp_rows: a row of <= 32768 tokens lives in one work-group's registers, a larger one in the output row (L2)
 
 
-def warp_rows(logits: torch.Tensor, rows: int, skip: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Temperature -> top-k -> top-p (HF warper semantics) in one launch.  logits [>= rows + skip, V]: logical row 0 is physical row 0,
-    logical row r > 0 is physical row r + skip (out row + the candidate rows behind the window rows).  Returns fp32 [rows, V] with the
-    removed tokens at -inf."""
+def _warp_rows_args(logits: torch.Tensor, rows: int, skip: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+    """the checks both warp entry points make before a raw pointer leaves; returns `out` (allocated when None)"""
     _dev(logits, "logits")
     assert logits.dim() == 2 and logits.stride(1) == 1
     V = logits.shape[1]
@@ -328,7 +325,34 @@ def warp_rows(logits: torch.Tensor, rows: int, skip: int, temperature: float = 1
     if out is None:
         out = torch.empty(rows, V, dtype=torch.float32, device=logits.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= rows * V
-    call("lade_warp_rows", ptr(logits), logits.stride(0), rows, V, dtype_code(logits), float(temperature), int(top_k), float(top_p), int(skip), ptr(out))
+    return out
+
+
+def warp_rows(logits: torch.Tensor, rows: int, skip: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+              out: Optional[torch.Tensor] = None, *, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0,
+              eta_cutoff: float = 0.0) -> torch.Tensor:
+    """Temperature -> top-k -> top-p -> min-p -> typical -> epsilon cutoff -> eta cutoff (HF warper semantics and order) in one launch.
+    logits [>= rows + skip, V]: logical row 0 is physical row 0, logical row r > 0 is physical row r + skip (out row + the candidate rows
+    behind the window rows).  Returns fp32 [rows, V] with the removed tokens at -inf.  The four keywords default to "off"; with all of them
+    off this is lade_warp_rows, else lade_warp_rows_ex."""
+    if min_p > 0.0 or typical_p < 1.0 or epsilon_cutoff > 0.0 or eta_cutoff > 0.0:
+        return _warp_rows_ex(logits, rows, skip, temperature, top_k, top_p, out, min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    out = _warp_rows_args(logits, rows, skip, out)
+    call("lade_warp_rows", ptr(logits), logits.stride(0), rows, logits.shape[1], dtype_code(logits), float(temperature), int(top_k), float(top_p),
+         int(skip), ptr(out))
+    return out[:rows] if out.dim() == 2 else out
+
+
+def _warp_rows_ex(logits: torch.Tensor, rows: int, skip: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                  out: Optional[torch.Tensor] = None, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0,
+                  eta_cutoff: float = 0.0) -> torch.Tensor:
+    """lade_warp_rows_ex as it is, whatever the values (with the four later stages off it runs the kernels of lade_warp_rows: the tests
+    compare the two entry points through this)"""
+    import ctypes as C
+    from .cabi import WarpParams
+    out = _warp_rows_args(logits, rows, skip, out)
+    params = WarpParams(float(temperature), int(top_k), float(top_p), float(min_p), float(typical_p), float(epsilon_cutoff), float(eta_cutoff))
+    call("lade_warp_rows_ex", ptr(logits), logits.stride(0), rows, logits.shape[1], dtype_code(logits), C.byref(params), int(skip), ptr(out))
     return out[:rows] if out.dim() == 2 else out
 
 

@@ -1,7 +1,8 @@
 """Sampling path: logits warpers and the host half of the multi-candidate rejection-sampling verify.
 
 Reference: lade/decoding.py:375-377 (admitted warpers: Temperature, TopK, TopP, applied through HF's LogitsProcessorList at
-:443, :488) and :484-540 (the verify loop, "modified from specinfer").
+:443, :488; here also the four HF builds behind them: min-p, typical, epsilon and eta cutoffs) and :484-540 (the verify loop,
+"modified from specinfer").
 
 Split of the work:
 
@@ -25,45 +26,81 @@ import torch
 
 
 class Warper:
-    """Temperature -> top-k -> top-p on [rows, V] fp32 logits (same order and tie rules as HF's TemperatureLogitsWarper /
-    TopKLogitsWarper / TopPLogitsWarper).  With top-k and top-p off the warp is a plain scale, which the device kernels apply
-    themselves (`fused_temperature`); otherwise the sampling loop calls `warp_rows` - one HIP launch (lade_warp_rows: no sort, no
-    topk; beyond 32768 tokens its output-row form) - and `__call__` (torch ops on whatever device the logits are on) remains for CPU
-    tensors and as the plain statement of the semantics."""
+    """Temperature -> top-k -> top-p -> min-p -> typical -> epsilon cutoff -> eta cutoff on [rows, V] fp32 logits: the order in which HF's
+    generate() builds its warpers and the tie rules of its classes (filter_value = -inf, min_tokens_to_keep = 1).  With everything but the
+    temperature off the warp is a plain scale, which the device kernels apply themselves (`fused_temperature`); otherwise the sampling
+    loop calls `warp_rows` - one HIP launch (lade_warp_rows / lade_warp_rows_ex: no sort, no topk) - and `__call__` (torch ops on whatever
+    device the logits are on: HF's own op sequences) remains for CPU tensors and as the plain statement of the semantics."""
 
-    def __init__(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+    def __init__(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, *, min_p: float = 0.0, typical_p: float = 1.0,
+                 epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0):
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k or 0), float(top_p)
+        self.min_p, self.typical_p = float(min_p or 0.0), float(1.0 if typical_p is None else typical_p)
+        self.epsilon_cutoff, self.eta_cutoff = float(epsilon_cutoff or 0.0), float(eta_cutoff or 0.0)
+
+    @property
+    def later_stages(self) -> bool:
+        """one of the four stages behind top-p is active"""
+        return self.min_p > 0.0 or self.typical_p < 1.0 or self.epsilon_cutoff > 0.0 or self.eta_cutoff > 0.0
 
     @property
     def fused_temperature(self) -> Optional[float]:
-        return self.temperature if (self.top_k <= 0 and self.top_p >= 1.0) else None
+        return self.temperature if (self.top_k <= 0 and self.top_p >= 1.0 and not self.later_stages) else None
 
     def warp_rows(self, logits: torch.Tensor, rows: int, skip: int) -> Optional[torch.Tensor]:
         """The warp of logical rows 0 and 1 + skip .. (the out row and the candidate rows of a step's logits) as ONE device launch
-        (lade_warp_rows); None for a CPU tensor or a vocabulary beyond 2^24 - the caller then uses __call__ (torch ops)."""
+        (lade_warp_rows, lade_warp_rows_ex with a later stage); None for a CPU tensor or a vocabulary beyond 2^24 - the caller then uses
+        __call__ (torch ops)."""
         from . import ops
         if not logits.is_cuda or logits.shape[-1] > ops.WARP_MAX_V:
             return None
-        return ops.warp_rows(logits, rows, skip, self.temperature, self.top_k, self.top_p)
+        return ops.warp_rows(logits, rows, skip, self.temperature, self.top_k, self.top_p, min_p=self.min_p, typical_p=self.typical_p,
+                             epsilon_cutoff=self.epsilon_cutoff, eta_cutoff=self.eta_cutoff)
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        ninf = -float("inf")
         if self.temperature != 1.0:
             x = x / self.temperature
         if self.top_k > 0:
             k = min(self.top_k, x.shape[-1])
             kth = torch.topk(x, k)[0][..., -1, None]
-            x = x.masked_fill(x < kth, -float("inf"))
+            x = x.masked_fill(x < kth, ninf)
         if self.top_p < 1.0:
             sl, si = torch.sort(x, descending=False)
             cp = sl.softmax(dim=-1).cumsum(dim=-1)
             rm = cp <= (1 - self.top_p)
             rm[..., -1:] = False
-            x = x.masked_fill(rm.scatter(-1, si, rm), -float("inf"))
+            x = x.masked_fill(rm.scatter(-1, si, rm), ninf)
+        if self.min_p > 0.0:                            # MinPLogitsWarper
+            p = torch.softmax(x, dim=-1)
+            rm = p < self.min_p * p.amax(dim=-1, keepdim=True)
+            rm.scatter_(-1, torch.topk(p, 1, dim=-1).indices, False)
+            x = x.masked_fill(rm, ninf)
+        if self.typical_p < 1.0:                        # TypicalLogitsWarper
+            normalized = torch.nn.functional.log_softmax(x, dim=-1)
+            ent = -(normalized * torch.exp(normalized)).nansum(-1, keepdim=True)
+            shifted = torch.abs((-normalized) - ent)
+            ss, si = torch.sort(shifted, descending=False)
+            cp = x.gather(-1, si).softmax(dim=-1).cumsum(dim=-1)
+            last = (cp < self.typical_p).sum(dim=-1, keepdim=True).clamp_(max=ss.shape[-1] - 1)
+            rm = ss > ss.gather(-1, last)
+            rm[..., :1] = False
+            x = x.masked_fill(rm.scatter(-1, si, rm), ninf)
+        if self.epsilon_cutoff > 0.0:                   # EpsilonLogitsWarper
+            rm = (x.softmax(dim=-1) < self.epsilon_cutoff) & (x < torch.topk(x, 1)[0][..., -1, None])
+            x = x.masked_fill(rm, ninf)
+        if self.eta_cutoff > 0.0:                       # EtaLogitsWarper (its epsilon is an fp32 tensor)
+            eps = torch.tensor(self.eta_cutoff, device=x.device)
+            entropy = torch.distributions.Categorical(logits=x).entropy()
+            eta = torch.min(eps, torch.sqrt(eps) * torch.exp(-entropy))[..., None]
+            rm = (x.softmax(dim=-1) < eta) & (x < torch.topk(x, 1)[0][..., -1, None])
+            x = x.masked_fill(rm, ninf)
         return x
 
 
-def make_warper(temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> Warper:
-    return Warper(temperature, top_k, top_p)
+def make_warper(temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, *, min_p: float = 0.0, typical_p: float = 1.0,
+                epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0) -> Warper:
+    return Warper(temperature, top_k, top_p, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
 
 
 @dataclass
