@@ -48,13 +48,11 @@
  *                            lade/models/modeling_llama.py:222-227, :360-380, :1164 ("next" row)
  *   lade_gemm_skinny / lade_gemm_skinny_kt / lade_weight_to_ktile / lade_weight_from_ktile / lade_splitk_reduce   the nn.Linear projections of the step at M = T <= 128 rows
  *                            lade/models/modeling_llama.py:360-380 (MLP), :492-494, :558 (q/k/v/o)
- *   lade_rope_kv_append_parts / lade_add_rmsnorm_parts / lade_silu_mul_parts   the same glue ops taking that
- *                            GEMM's fp32 split-K partials as input (the reduction is fused into the consumer)
- *   lade_rope_kv_append_ex / lade_rope_kv_append_parts_ex   the two RoPE + KV append entry points with the qkv epilogue of
- *                            Qwen2 (q / k / v bias) and Qwen3 (per-head RMSNorm of q and k before RoPE); the reference adapts
- *                            Llama only
- *   lade_gen_ctl_init / lade_gen_ctl_update / lade_gen_argmax / lade_gen_rows / lade_greedy_post_step_ex   HF's repetition penalty,
- *                            min-length processors and EOS sets on the step's rows (the reference refuses them, lade/decoding.py:968)
+ *                            lade_rope_kv_append, lade_add_rmsnorm and lade_silu_mul also take that GEMM's fp32 split-K partials as
+ *                            their input (the reduction is fused into the consumer); lade_rope_kv_append carries the qkv epilogue of
+ *                            Qwen2 (q / k / v bias) and Qwen3 (per-head RMSNorm of q and k before RoPE) - the reference adapts Llama only
+ *   lade_gen_ctl_init / lade_gen_ctl_update / lade_gen_argmax / lade_gen_rows   HF's repetition penalty and min-length processors on the
+ *                            step's rows; lade_greedy_post_step takes a set of EOS ids (the reference refuses them, lade/decoding.py:968)
  *   lade_emit_init / lade_emit_rows   the `scores` / `logits` tuples of generate(return_dict_in_generate=True): the reference refuses them
  *                            (lade/decoding.py:967 greedy, the matching assertion at the head of jacobi_sample_multilevel's loop for sampling)
  *   lade_time_attn / lade_time_attn_rot   hipEvent timing helpers for bench.py (no reference counterpart)
@@ -68,12 +66,15 @@
 extern "C" {
 #endif
 
-#define LADE_ABI_VERSION 4      /* 2: lade_attn_args grew (wg_rows, fused RoPE), lade_gemm_skinny* take `ring`, lade_greedy_post_step takes record_host;
+#define LADE_ABI_VERSION 5      /* 2: lade_attn_args grew (wg_rows, fused RoPE), lade_gemm_skinny* take `ring`, lade_greedy_post_step takes record_host;
                                  * 3: + lade_gemm_ra_kt, lade_build_flags; + lade_gen_ctl_init, lade_gen_ctl_update, lade_gen_argmax,
                                  *    lade_gen_rows, lade_greedy_post_step_ex (nothing that existed changed);
                                  * 4: the measured-and-dropped kernels are gone: lade_attn_args ends at wg_rows (n_parts, qkv_parts, part_stride, positions,
                                  *    cos_tab, sin_tab, max_pos, sync_flags removed), lade_gemm_ra_kt and lade_build_flags removed; nothing else changed
-                                 *    (+ lade_emit_init, lade_emit_rows since: nothing that existed changed, the number stays) */
+                                 *    (+ lade_emit_init, lade_emit_rows);
+                                 * 5: one entry point per kernel family, the source and the optional stages chosen by nullable arguments: lade_rope_kv_append
+                                 *    (was + _ex, _parts, _parts_ex), lade_greedy_post_step (takes the EOS set; _ex removed), lade_add_rmsnorm (was + _parts,
+                                 *    _rows), lade_silu_mul (was + _parts) */
 
 /* error codes */
 #define LADE_OK 0
@@ -194,15 +195,33 @@ int lade_rope_rows_dynamic(const int32_t* positions, int32_t T, int32_t P, const
                            int32_t max_position_embeddings, const float* inv_tab, int32_t n_len, int32_t d, void* cos_rows, void* sin_rows,
                            int32_t dtype, const int32_t* g_dev, int32_t gcap, int32_t gs, void* stream);
 
-/* qkv: [T][(H+2*Hkv)*d] fused projection output.  Rotates q in place and writes the rotated k
- * and v of token t into cache row P+t.  cos/sin: [max_pos][d] tables in the model dtype, built
- * as the reference builds them (fp32 math, then cast; modeling_llama.py:248-256); the rotation
- * reproduces the reference's per-op rounding: round(q*cos) + round(rotate_half(q)*sin), rounded.
- * positions: device int32[T] (explicit, non-monotone position ids).  P from `dyn_P` if non-null. */
-int lade_rope_kv_append(void* qkv, const int32_t* positions, const void* cos_tab, const void* sin_tab,
-                        void* k_cache, void* vt_cache, int32_t T, int32_t P, const int32_t* dyn_P,
-                        int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
-                        void* stream);
+/* RoPE of q and k fused with the KV append: the rotated k and the v of token t go to cache row P+t.  cos/sin: [max_pos][d] tables in the
+ * model dtype, built as the reference builds them (fp32 math, then cast; modeling_llama.py:248-256); the rotation reproduces the
+ * reference's per-op rounding: round(q*cos) + round(rotate_half(q)*sin), rounded.  positions: device int32[T] (explicit, non-monotone
+ * position ids).  P from `dyn_P` if non-null.
+ * The source of q / k / v - exactly one of the two, both or neither is LADE_E_ARG:
+ *   qkv     [T][(H+2*Hkv)*d], the materialised fused projection; q is rotated in place (n_parts, part_stride, q_out are ignored).  d even;
+ *           all three dtypes.
+ *   parts   the same projection as n_parts >= 1 fp32 split-K partials [n_parts][T][(H+2*Hkv)*d], part_stride elements apart, summed in
+ *           split order and rounded once to the model dtype; the rotated q goes to q_out [T][H*d] (required).  (d/2) % 8 == 0; bf16 / f16
+ *           only (LADE_E_DTYPE otherwise).
+ * epi (nullable; one whose three pointers are null counts as null: exactly the plain kernel) - the qkv epilogue of Qwen2 / Qwen3, applied
+ * per token and head between the projection and RoPE; a null field skips its step:
+ *   bias    [(H + 2*Hkv)*d] model dtype, added to q, k and v: to the fp32 sum of the partials before its single rounding (F.linear with a
+ *           bias), or to the already rounded qkv with one more rounding;
+ *   q_norm, k_norm   [d] model dtype: Qwen3RMSNorm over each q / k head, x -> round(w * round(x * rsqrt(mean(x^2) + eps))), the mean in
+ *           fp32, 0 <= eps < 1; RoPE runs on the result.  V gets the bias only.
+ * The three pointers 16-byte aligned.  The head norm on `parts` needs d / 16 to be a power of two. */
+typedef struct lade_qkv_epilogue {
+    const void* bias;
+    const void* q_norm;
+    const void* k_norm;
+    float eps;
+} lade_qkv_epilogue;
+int lade_rope_kv_append(void* qkv, const float* parts, int32_t n_parts, int64_t part_stride, void* q_out, const int32_t* positions,
+                        const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int32_t T, int32_t P,
+                        const int32_t* dyn_P, int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
+                        const lade_qkv_epilogue* epi, void* stream);
 
 /* Copies `cnt` K/V rows src..src+cnt -> dst..dst+cnt in every layer of a [L][2] cache whose
  * K part is [Hkv][S_max][d] and V part [Hkv][d][S_max]; layer_stride / v_offset in elements.
@@ -287,7 +306,9 @@ int lade_window_roll(int32_t* window, int32_t wcap, int32_t* ctl, const int32_t*
  * memory takes them as they are issued, in any order): the seal, computed over all the other words, is the only ordering guarantee - a
  * reader accepts a record only when the step number AND the seal match what it read, and must bound its wait (memory the device's stores do
  * not reach coherently never shows the record).
- * eos < 0 disables the EOS scan; the scan follows lade/decoding.py:1167-1177.
+ * eos_set: HOST array of n_eos end-of-sequence ids (0..LADE_GEN_MAX_EOS, each >= 0; null allowed when n_eos == 0), copied into the
+ * launch.  The EOS scan (lade/decoding.py:1167-1177) stops at the first accepted token that is in the set; the tokens accepted after it in
+ * the same step are dropped.  n_eos == 0 disables the scan.
  * Sampling (lade/decoding.py:137-692): the rejection-sampling verify runs on the host (it consumes the python
  * and torch RNG streams in the reference's order); its result is passed as forced = {max_hit, max_hit_idx,
  * hits[gs]} (device) and replaces the greedy verify; level_override[W] (device, -1 = keep) carries the
@@ -295,17 +316,8 @@ int lade_window_roll(int32_t* window, int32_t wcap, int32_t* ctl, const int32_t*
 int lade_greedy_post_step(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* pool_tok, int32_t* pool_cnt,
                           int32_t V, int32_t W, int32_t N, int32_t G, const int32_t* am, int32_t n_inp,
                           int32_t* guess, int32_t T_step, int32_t cand_rows, int32_t phase, int32_t pool_from_prompt,
-                          int32_t* tail, int32_t eos, const int32_t* forced, const int32_t* level_override,
-                          int32_t* record, int32_t* record_host, void* stream);
-
-/* The same with a SET of end-of-sequence ids: eos_set = host array of n_eos ids (0..LADE_GEN_MAX_EOS, each >= 0), copied into the
- * launch.  The EOS scan stops at the first accepted token that is in the set; the tokens accepted after it in the same step are
- * dropped.  lade_greedy_post_step(..., eos, ...) launches the same kernel with the set {eos} (empty when eos < 0). */
-int lade_greedy_post_step_ex(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* pool_tok, int32_t* pool_cnt,
-                             int32_t V, int32_t W, int32_t N, int32_t G, const int32_t* am, int32_t n_inp,
-                             int32_t* guess, int32_t T_step, int32_t cand_rows, int32_t phase, int32_t pool_from_prompt,
-                             int32_t* tail, const int32_t* eos_set, int32_t n_eos, const int32_t* forced,
-                             const int32_t* level_override, int32_t* record, int32_t* record_host, void* stream);
+                          int32_t* tail, const int32_t* eos_set, int32_t n_eos, const int32_t* forced,
+                          const int32_t* level_override, int32_t* record, int32_t* record_host, void* stream);
 
 /* ---- generation controls (HF's RepetitionPenaltyLogitsProcessor, MinLengthLogitsProcessor / MinNewTokensLengthLogitsProcessor) ----
  * The controls of one sequence live in a device block of int32 words `gen` (LADE_GEN_WORDS(V)), never in kernel arguments: a captured
@@ -351,7 +363,7 @@ int lade_gen_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, int32
                   const int32_t* gen, const int32_t* ctl, const int32_t* guess, const int32_t* pos, const int32_t* sel,
                   int32_t* am, float* rows_out, void* stream);
 
-/* ---- emitted rows (generate(return_dict_in_generate=True, output_scores / output_logits); additive to ABI 4) --------------------------
+/* ---- emitted rows (generate(return_dict_in_generate=True, output_scores / output_logits)) ---------------------------------------------
  * HF returns, per generated token, the fp32 row that decided it: `logits` = the model's row (`.to(float32)`), `scores` = that row after
  * the logits processors / warpers.  A lookahead step emits 1 .. gs + 1 tokens; which rows decided them:
  *   token 0 of a step      the out row:                       raw row 0,                         processed row 0
@@ -389,9 +401,9 @@ int lade_emit_rows(int64_t* desc, const void* raw, int64_t raw_ld, int32_t raw_d
  * rec_words >= 4 + split + g_local*gs.  The candidates are verified inside lade_lp_reduce_apply, on the gathered rows,
  * against RANK 0's first token - the reference broadcasts `next_tokens` from rank 0 before verifying
  * (lade/decoding.py:1024, :1071-1096) - so every rank takes the same decision even when 16-bit logits round
- * differently from rank to rank.  scratch: int32[R*split + G*gs].  pool_from_prompt / tail / eos: as in
+ * differently from rank to rank.  scratch: int32[R*split + G*gs].  pool_from_prompt / tail: as in
  * lade_greedy_post_step (the EOS scan and the POOL_FROM_PROMPT appends of lade/decoding.py:1167-1177 run identically on
- * every rank); record[1] = n_accept, record[2] = finished, record[5] = winning rank.  lade_lp_pack with ctl != NULL derives g_local
+ * every rank; eos: ONE end-of-sequence id, < 0 = no scan); record[1] = n_accept, record[2] = finished, record[5] = winning rank.  lade_lp_pack with ctl != NULL derives g_local
  * from ctl[LADE_CTL_G] and (lp_rank, lp_world) on the device (graph replay; pass g_local = the padded row count's candidates). */
 int lade_lp_pack(const int32_t* am_out, const int32_t* am_inp, int32_t n_inp, const int32_t* am_guess, int32_t g_local,
                  int32_t gs, int32_t split, int32_t* rec, int32_t rec_words, const int32_t* ctl, int32_t lp_rank, int32_t lp_world,
@@ -477,21 +489,27 @@ int lade_rmsnorm(const void* x, const void* weight, void* y, int32_t rows, int32
  * (:857): x[r] = table[ids[r]] (ids clamped to the table), y[r] = rmsnorm(x[r]) - one launch instead of a row gather and a norm */
 int lade_embed_rmsnorm(const void* table, int32_t table_rows, const int32_t* ids, void* x, const void* weight, void* y, int32_t rows,
                        int32_t hidden, float eps, int32_t dtype, void* stream);
-/* y = x + r (residual add) fused with the norm of the sum: x <- x + r ; y = rmsnorm(x) */
-int lade_add_rmsnorm(void* x, const void* r, const void* weight, void* y, int32_t rows, int32_t hidden, float eps,
-                     int32_t dtype, void* stream);
-/* The row-pruned tail of a step (the reference norms and projects all T rows, lade/models/modeling_llama.py:1541-1544; only the out row,
- * the last level's rows and the candidate rows are ever read): y[j] = rmsnorm(x[sel[j]] + res[sel[j]]) for j < n_sel, res = r or the sum of
- * n_parts fp32 split-K partials (part_stride elements apart) in split order; x is NOT written back.  One launch instead of a partial
- * fold, two row gathers and a norm. */
-int lade_add_rmsnorm_rows(const void* x, const void* r, const float* parts, int32_t n_parts, int64_t part_stride, const int32_t* sel,
-                          const void* weight, void* y, int32_t n_sel, int32_t src_rows, int32_t hidden, float eps, int32_t dtype,
-                          void* stream);
+/* Residual add fused with the norm of the sum: y = rmsnorm(x + res).
+ * The residual - exactly one of the two, both or neither is LADE_E_ARG:
+ *   r       the residual rows in the model dtype;
+ *   parts   a GEMM output as n_parts >= 1 fp32 split-K partials [n_parts][rows of x][hidden], part_stride elements apart, summed in split
+ *           order and rounded once to the model dtype - the split-K GEMM needs no reduce pass.  bf16 / f16 only (LADE_E_DTYPE otherwise).
+ * sel (nullable) selects the rows:
+ *   null    every row r < rows: x[r] <- x[r] + res[r] in place, y[r] = rmsnorm(x[r]); src_rows is ignored;
+ *   sel     device int32[rows], the row-pruned tail of a step (the reference norms and projects all T rows, lade/models/modeling_llama.py:
+ *           1541-1544; only the out row, the last level's rows and the candidate rows are ever read): y[j] = rmsnorm(x[sel[j]] + res[sel[j]])
+ *           for j < rows, x [src_rows][hidden] is read only.  One launch instead of a partial fold, two row gathers and a norm. */
+int lade_add_rmsnorm(void* x, const void* r, const float* parts, int32_t n_parts, int64_t part_stride, const int32_t* sel, int32_t src_rows,
+                     const void* weight, void* y, int32_t rows, int32_t hidden, float eps, int32_t dtype, void* stream);
 /* SwiGLU of LlamaMLP (lade/models/modeling_llama.py:360-380) on the output of the fused gate/up GEMM, rounded like the separate torch ops.
  * layout 0: gu rows are [gate (inter) | up (inter)]: out[r][i] = silu(gu[r][i]) * gu[r][inter + i].
  * layout 1: groups of 16 - [16 gate | their 16 up] per 32 columns: out[r][i] = silu(gu[r][32*(i/16) + i%16]) * gu[r][32*(i/16) + 16 + i%16]
- *           (the row order in which the step engine fuses the two weights, so that lade_gemm_skinny's SwiGLU epilogue is lane-local). */
-int lade_silu_mul(const void* gu, void* out, int32_t rows, int32_t inter, int32_t layout, int32_t dtype, void* stream);
+ *           (the row order in which the step engine fuses the two weights, so that lade_gemm_skinny's SwiGLU epilogue is lane-local).
+ * The input - exactly one of the two, both or neither is LADE_E_ARG: gu [rows][2*inter] in the model dtype, or that GEMM output as n_parts >= 1
+ * fp32 split-K partials [n_parts][rows][2*inter], part_stride elements apart, summed in split order and rounded once to the model dtype
+ * (bf16 / f16 only: LADE_E_DTYPE otherwise). */
+int lade_silu_mul(const void* gu, const float* parts, int32_t n_parts, int64_t part_stride, void* out, int32_t rows, int32_t inter, int32_t layout,
+                  int32_t dtype, void* stream);
 /* dst[r][:] = src[idx[r]][:]  (row gather: embedding lookup, logits-row selection) */
 int lade_gather_rows(const void* src, const int32_t* idx, void* dst, int32_t rows, int32_t width, int32_t elem_bytes,
                      int32_t src_rows, void* stream);
@@ -527,39 +545,8 @@ int lade_weight_to_ktile(const void* W, int64_t ldw, void* Wkt, int32_t N, int32
 /* the inverse, into a caller-provided row-major scratch W[N][ldw]: what a library GEMM needs (prefill chunks wider than 256 rows) when a
  * model too large to be held twice keeps its projection weights K-tile-major only */
 int lade_weight_from_ktile(const void* Wkt, void* W, int64_t ldw, int32_t N, int32_t K, int32_t dtype, void* stream);
-/* consumers that take a GEMM output as n_parts fp32 split-K partials [n_parts][rows][width] (part_stride elements
- * apart), sum them in split order and round once to the model dtype - so the split-K GEMM needs no reduce pass */
-int lade_add_rmsnorm_parts(void* x, const float* parts, int32_t n_parts, int64_t part_stride, const void* weight, void* y,
-                           int32_t rows, int32_t hidden, float eps, int32_t dtype, void* stream);
-int lade_silu_mul_parts(const float* parts, int32_t n_parts, int64_t part_stride, void* out, int32_t rows, int32_t inter,
-                        int32_t layout, int32_t dtype, void* stream);
-int lade_rope_kv_append_parts(const float* parts, int32_t n_parts, int64_t part_stride, void* q_out, const int32_t* positions,
-                              const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int32_t T, int32_t P,
-                              const int32_t* dyn_P, int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos,
-                              int32_t dtype, void* stream);
-/* ---- qkv epilogue of RoPE + KV append (Qwen2 / Qwen3; additive to ABI 3) -------------------------------------------
- * Applied per token and head between the qkv projection and RoPE; a null field skips its step:
- *   bias    [(H + 2*Hkv)*d] model dtype, added to q, k and v: to the fp32 sum of the partials before its single rounding
- *           (lade_rope_kv_append_parts_ex: F.linear with a bias), to the already rounded projection with one more rounding
- *           (lade_rope_kv_append_ex);
- *   q_norm, k_norm   [d] model dtype: Qwen3RMSNorm over each q / k head, x -> round(w * round(x * rsqrt(mean(x^2) + eps))), the
- *           mean in fp32; RoPE runs on the result.  V gets the bias only.
- * All pointers 16-byte aligned.  A null `epi` (or one whose three pointers are null) launches exactly the plain kernel.  The
- * head norm on the partials path needs d / 16 to be a power of two. */
-typedef struct lade_qkv_epilogue {
-    const void* bias;
-    const void* q_norm;
-    const void* k_norm;
-    float eps;
-} lade_qkv_epilogue;
-int lade_rope_kv_append_ex(void* qkv, const int32_t* positions, const void* cos_tab, const void* sin_tab,
-                           void* k_cache, void* vt_cache, int32_t T, int32_t P, const int32_t* dyn_P,
-                           int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
-                           const lade_qkv_epilogue* epi, void* stream);
-int lade_rope_kv_append_parts_ex(const float* parts, int32_t n_parts, int64_t part_stride, void* q_out, const int32_t* positions,
-                                 const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int32_t T, int32_t P,
-                                 const int32_t* dyn_P, int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos,
-                                 int32_t dtype, const lade_qkv_epilogue* epi, void* stream);
+/* the reduce pass of a split-K GEMM whose consumer does not take the partials itself (lade_rope_kv_append, lade_add_rmsnorm and
+ * lade_silu_mul do): C = the n_split partials summed in split order, rounded once to the model dtype */
 int lade_splitk_reduce(const float* part, void* C, int64_t ldc, int32_t M, int32_t N, int32_t n_split, int32_t dtype,
                        void* stream);
 

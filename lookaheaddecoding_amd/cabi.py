@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LADE_HIP_LIB") or os.path.join(_HERE, "liblade_hip.so")     # env override: kernel experiments
 
-ABI_VERSION = 4           # LADE_ABI_VERSION of include/lade_hip.h this binding was written against (checked at load time)
+ABI_VERSION = 5           # LADE_ABI_VERSION of include/lade_hip.h this binding was written against (checked at load time)
 LADE_BF16, LADE_F16, LADE_F32 = 0, 1, 2
 DTYPE_CODE = {torch.bfloat16: LADE_BF16, torch.float16: LADE_F16, torch.float32: LADE_F32}
 
@@ -83,7 +83,8 @@ SIGNATURES = {
     "lade_attn_combine": [C.POINTER(AttnArgs), _vp],
     "lade_attn_prefill": [C.POINTER(AttnArgs), _vp],
     "lade_mask_render": [C.POINTER(MaskParams), _vp, _vp],
-    "lade_rope_kv_append": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "lade_rope_kv_append": [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                            C.POINTER(QkvEpilogue), _vp],
     "lade_rope_rows_dynamic": [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp],
     "lade_kv_commit": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp],
     "lade_kv_pack_bshd": [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
@@ -99,9 +100,7 @@ SIGNATURES = {
     "lade_window_fill": [_vp, _i32, _vp, _i32, _vp, _i32, _vp],
     "lade_window_roll": [_vp, _i32, _vp, _vp, _i32, _i32, _vp],
     "lade_greedy_post_step": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp,
-                              _i32, _vp, _vp, _vp, _vp, _vp],
-    "lade_greedy_post_step_ex": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp,
-                                 _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+                              _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "lade_gen_ctl_init": [_vp, _i32, C.c_double, _i32, _vp, _i32, _vp, _i32, _vp],
     "lade_gen_ctl_update": [_vp, _vp, _vp],
     "lade_gen_argmax": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -121,20 +120,13 @@ SIGNATURES = {
     "lade_warp_rows_ex": [_vp, _i64, _i32, _i32, _i32, C.POINTER(WarpParams), _i32, _vp, _vp],
     "lade_rmsnorm": [_vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
     "lade_embed_rmsnorm": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
-    "lade_add_rmsnorm": [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
-    "lade_add_rmsnorm_rows": [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp],
-    "lade_silu_mul": [_vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "lade_add_rmsnorm": [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
+    "lade_silu_mul": [_vp, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
     "lade_gather_rows": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "lade_gemm_skinny": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "lade_gemm_skinny_kt": [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "lade_weight_to_ktile": [_vp, _i64, _vp, _i32, _i32, _i32, _vp],
     "lade_weight_from_ktile": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
-    "lade_add_rmsnorm_parts": [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
-    "lade_silu_mul_parts": [_vp, _i32, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
-    "lade_rope_kv_append_parts": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "lade_rope_kv_append_ex": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(QkvEpilogue), _vp],
-    "lade_rope_kv_append_parts_ex": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
-                                     C.POINTER(QkvEpilogue), _vp],
     "lade_splitk_reduce": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
     "lade_record_seal": [C.POINTER(C.c_uint32), C.c_uint32],
     "lade_version": [],

@@ -92,6 +92,18 @@ __device__ __forceinline__ uint32_t pack2<F16>(float lo, float hi) {
     return (uint32_t)from_f32<F16>(lo) | ((uint32_t)from_f32<F16>(hi) << 16);
 }
 
+// host: the one dispatch on a LADE_BF16 / LADE_F16 / LADE_F32 code.  f(tag) runs with the tag type's value (`[&](auto t) { typedef decltype(t) T; .. }`);
+// false = not one of the three, and nothing ran: the entry point refuses the code with its own error and message.
+template <typename F>
+static inline bool dispatch_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case LADE_BF16: f(BF16{}); return true;
+        case LADE_F16: f(F16{}); return true;
+        case LADE_F32: f(F32{}); return true;
+    }
+    return false;
+}
+
 // torch.argmax's order, one definition for lade_argmax_rows, lade_argmax_pairs and the lm_head GEMM's argmax epilogue: a NaN is the maximum
 // (the first NaN of a row wins), among equal values the lowest index wins; bi == 0x7fffffff = nothing seen yet
 __device__ __forceinline__ bool argmax_better(float v, int i, float best, int bi) {

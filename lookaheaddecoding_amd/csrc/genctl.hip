@@ -176,18 +176,10 @@ static int launch_rows(const char* fn, const void* logits, int64_t ld, int32_t r
                  "%s: %d candidate rows are not whole candidates of gs=%d (<= %d), or no guess buffer", fn, cand_rows, gs, LADE_MAX_GUESS_SET);
     const size_t lds = (size_t)((V + 31) / 32) * 4;
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case LADE_BF16:
-            hipLaunchKernelGGL((gen_rows_kernel<BF16, ROWS>), dim3(rows), dim3(1024), lds, st, logits, ld, V, n_inp, gs, gen, ctl, guess, pos, sel, am, rows_out);
-            break;
-        case LADE_F16:
-            hipLaunchKernelGGL((gen_rows_kernel<F16, ROWS>), dim3(rows), dim3(1024), lds, st, logits, ld, V, n_inp, gs, gen, ctl, guess, pos, sel, am, rows_out);
-            break;
-        case LADE_F32:
-            hipLaunchKernelGGL((gen_rows_kernel<F32, ROWS>), dim3(rows), dim3(1024), lds, st, logits, ld, V, n_inp, gs, gen, ctl, guess, pos, sel, am, rows_out);
-            break;
-        default: LADE_REQUIRE(false, LADE_E_DTYPE, "%s: dtype=%d", fn, dtype);
-    }
+    const bool known = dispatch_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL((gen_rows_kernel<decltype(t), ROWS>), dim3(rows), dim3(1024), lds, st, logits, ld, V, n_inp, gs, gen, ctl, guess, pos, sel, am, rows_out);
+    });
+    LADE_REQUIRE(known, LADE_E_DTYPE, "%s: dtype=%d", fn, dtype);
     return check_launch(fn);
 }
 

@@ -6,19 +6,6 @@
 
 namespace lade {
 
-template <typename T> struct St;
-template <> struct St<BF16> { typedef uint16_t S; };
-template <> struct St<F16> { typedef uint16_t S; };
-template <> struct St<F32> { typedef float S; };
-template <typename T> __device__ __forceinline__ float ldf(const typename St<T>::S* p, size_t i);
-template <> __device__ __forceinline__ float ldf<BF16>(const uint16_t* p, size_t i) { return to_f32<BF16>(p[i]); }
-template <> __device__ __forceinline__ float ldf<F16>(const uint16_t* p, size_t i) { return to_f32<F16>(p[i]); }
-template <> __device__ __forceinline__ float ldf<F32>(const float* p, size_t i) { return p[i]; }
-template <typename T> __device__ __forceinline__ typename St<T>::S stf(float f);
-template <> __device__ __forceinline__ uint16_t stf<BF16>(float f) { return from_f32<BF16>(f); }
-template <> __device__ __forceinline__ uint16_t stf<F16>(float f) { return from_f32<F16>(f); }
-template <> __device__ __forceinline__ float stf<F32>(float f) { return f; }
-
 __device__ __forceinline__ float block_sum(float v, float* sm) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -120,7 +107,7 @@ __device__ __forceinline__ void load_parts_r(const float* parts, int n_parts, si
             }
     }
 #pragma unroll
-    for (int e = 0; e < N; ++e) { const typename St<T>::S sv = stf<T>(out[e]); out[e] = ldf<T>(&sv, 0); }
+    for (int e = 0; e < N; ++e) out[e] = Elem<T>::ld(Elem<T>::st(out[e]));
 }
 
 template <typename T, int N>
@@ -130,15 +117,15 @@ __device__ __forceinline__ void load_parts(const float* parts, int n_parts, size
 }
 
 // value after one rounding to the storage type
-template <typename T> __device__ __forceinline__ float rnd_st(float f) { typename St<T>::S s = stf<T>(f); return ldf<T>(&s, 0); }
+template <typename T> __device__ __forceinline__ float rnd_st(float f) { return Elem<T>::ld(Elem<T>::st(f)); }
 
 // y = w * cast(x_f32 * rsqrt(mean(x^2)+eps));  ADD: x <- cast(x + r) first (residual), norm of the sum.
 // One block of BT threads per row, the row lives in registers (<= CH 16-byte chunks per thread): one HBM pass.
 // Latency bound (rows <= 240): every load of the row - x, the residual or all its split-K partials, the norm
 // weight - is issued before the first use.
 template <typename T, bool ADD, int CH, int BT>
-__global__ __launch_bounds__(BT) void rmsnorm_kernel(typename St<T>::S* x, const typename St<T>::S* r, const typename St<T>::S* w,
-                                                     typename St<T>::S* y, int hidden, float eps, const float* parts, int n_parts,
+__global__ __launch_bounds__(BT) void rmsnorm_kernel(typename Elem<T>::S* x, const typename Elem<T>::S* r, const typename Elem<T>::S* w,
+                                                     typename Elem<T>::S* y, int hidden, float eps, const float* parts, int n_parts,
                                                      size_t part_stride, const int32_t* sel = nullptr, int src_rows = 0) {
     constexpr int N = Vec<T>::N;
     __shared__ float sm[BT / 64];
@@ -157,7 +144,7 @@ __global__ __launch_bounds__(BT) void rmsnorm_kernel(typename St<T>::S* x, const
     float ss = 0.f;
     // without ADD, `r` may name a row table (the embedding matrix, lade_embed_rmsnorm): the block's input row is r[sel[blockIdx.x]] and
     // is also copied to x[blockIdx.x] - the step's embedding gather and its first norm in one launch (modeling_llama.py:1413, :857)
-    const typename St<T>::S* xin = (!ADD && r) ? r : x;
+    const typename Elem<T>::S* xin = (!ADD && r) ? r : x;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
         const int i = threadIdx.x + c * BT;
@@ -199,7 +186,7 @@ __global__ __launch_bounds__(BT) void rmsnorm_kernel(typename St<T>::S* x, const
 // layout 0: a row is [gate (inter) | up (inter)] (two projections concatenated); layout 1: groups of 16 - [16 gate | their 16 up] - the
 // row order of the engine's fused gate/up weight (see the SwiGLU epilogue of gemm.hip)
 template <typename T>
-__global__ __launch_bounds__(256) void silu_mul_kernel(const typename St<T>::S* gu, typename St<T>::S* out, int inter, const float* parts,
+__global__ __launch_bounds__(256) void silu_mul_kernel(const typename Elem<T>::S* gu, typename Elem<T>::S* out, int inter, const float* parts,
                                                        int n_parts, size_t part_stride, int layout) {
     constexpr int N = Vec<T>::N;
     const size_t rb = (size_t)blockIdx.y * 2 * inter;
@@ -233,16 +220,16 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const unsigned char* s
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void softmax_rows_kernel(const typename St<T>::S* logits, int64_t ld, int V, float inv_temp, float* probs) {
+__global__ __launch_bounds__(256) void softmax_rows_kernel(const typename Elem<T>::S* logits, int64_t ld, int V, float inv_temp, float* probs) {
     __shared__ float sm[8];
     const size_t base = (size_t)blockIdx.x * ld;
     float* out = probs + (size_t)blockIdx.x * V;
     float mx = -INFINITY;
-    for (int i = threadIdx.x; i < V; i += blockDim.x) mx = fmaxf(mx, ldf<T>(logits, base + i) * inv_temp);
+    for (int i = threadIdx.x; i < V; i += blockDim.x) mx = fmaxf(mx, Elem<T>::ld(logits[base + i]) * inv_temp);
     mx = block_max(mx, sm);
     float s = 0.f;
     for (int i = threadIdx.x; i < V; i += blockDim.x) {
-        const float e = expf(ldf<T>(logits, base + i) * inv_temp - mx);
+        const float e = expf(Elem<T>::ld(logits[base + i]) * inv_temp - mx);
         out[i] = e;
         s += e;
     }
@@ -256,7 +243,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const typename St<T>:
 // three dependent scalar sweeps above cost 97 us for a 32000-entry row (a quarter-occupied CU walking 125 elements per thread three
 // times), this form ~6 us.  Used when the row is 16-byte aligned and V a multiple of the vector width.
 template <typename T, int CH>
-__global__ __launch_bounds__(1024) void softmax_rows_vec_kernel(const typename St<T>::S* logits, int64_t ld, int V, float inv_temp, float* probs) {
+__global__ __launch_bounds__(1024) void softmax_rows_vec_kernel(const typename Elem<T>::S* logits, int64_t ld, int V, float inv_temp, float* probs) {
     constexpr int N = Vec<T>::N;
     __shared__ float sm[16];
     const size_t base = (size_t)blockIdx.x * ld;
@@ -303,7 +290,7 @@ __global__ __launch_bounds__(1024) void softmax_rows_vec_kernel(const typename S
 // of logits/temperature) in one sweep over the V logits, then the g probabilities are gathered; the [rows, V] probability
 // matrix the reference materialises (guess_probs, 15 MB per step at config 3) is never written.
 template <typename T>
-__global__ __launch_bounds__(1024) void softmax_gather_kernel(const typename St<T>::S* logits, int64_t ld, int V, float inv_temp, int skip,
+__global__ __launch_bounds__(1024) void softmax_gather_kernel(const typename Elem<T>::S* logits, int64_t ld, int V, float inv_temp, int skip,
                                                               const int32_t* guess, const int32_t* g_dev, int g_host, int gs, int g_cap,
                                                               float* scal, float* stats) {
     __shared__ float sm[16];
@@ -318,7 +305,7 @@ __global__ __launch_bounds__(1024) void softmax_gather_kernel(const typename St<
     // online max / sum: one pass over the row
     float mx = -INFINITY, sum = 0.f;
     for (int i = threadIdx.x; i < V; i += blockDim.x) {
-        const float x = ldf<T>(logits, base + i) * inv_temp;
+        const float x = Elem<T>::ld(logits[base + i]) * inv_temp;
         if (x > mx) { sum = sum * expf(mx - x) + 1.f; mx = x; }
         else if (x > -INFINITY) sum += expf(x - mx);
     }
@@ -330,7 +317,7 @@ __global__ __launch_bounds__(1024) void softmax_gather_kernel(const typename St<
         for (int c = threadIdx.x; c < g; c += blockDim.x) {
             int tok = guess[c * gs + pos];
             tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
-            scal[(size_t)row * g_cap + c] = expf(ldf<T>(logits, base + tok) * inv_temp - bm) / bs;
+            scal[(size_t)row * g_cap + c] = expf(Elem<T>::ld(logits[base + tok]) * inv_temp - bm) / bs;
         }
 }
 
@@ -338,24 +325,21 @@ __global__ __launch_bounds__(1024) void softmax_gather_kernel(const typename St<
 
 using namespace lade;
 
-
-#define DISPATCH_DTYPE(dtype, CALL)                                   \
-    switch (dtype) {                                                  \
-        case LADE_BF16: { typedef BF16 TT; CALL; } break;             \
-        case LADE_F16: { typedef F16 TT; CALL; } break;               \
-        case LADE_F32: { typedef F32 TT; CALL; } break;               \
-        default: LADE_REQUIRE(false, LADE_E_DTYPE, "unsupported dtype %d", dtype); \
-    }
-
 template <bool ADD>
 static int launch_rmsnorm(void* x, const void* r, const void* weight, void* y, int rows, int hidden, float eps, int dtype, hipStream_t st,
                           const float* parts = nullptr, int n_parts = 0, size_t part_stride = 0, const int32_t* sel = nullptr, int src_rows = 0) {
+    const char* who = ADD ? "lade_add_rmsnorm" : "lade_rmsnorm";
     const int nvec_bytes = dtype == LADE_F32 ? 4 : 8;
-    LADE_REQUIRE(hidden % nvec_bytes == 0, LADE_E_ARG, "lade_rmsnorm: hidden=%d must be a multiple of %d", hidden, nvec_bytes);
+    LADE_REQUIRE(hidden % nvec_bytes == 0, LADE_E_ARG, "%s: hidden=%d must be a multiple of %d", who, hidden, nvec_bytes);
     const int vecs = hidden / nvec_bytes;              // 16-byte chunks per row
-    LADE_REQUIRE(vecs <= 4 * 1024, LADE_E_LIMIT, "lade_rmsnorm: hidden=%d too large for the register-resident row", hidden);
-#define RMS_LAUNCH(CH, BT) DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((rmsnorm_kernel<TT, ADD, CH, BT>), dim3(rows), dim3(BT), 0, st, (St<TT>::S*)x, \
-                                          (const St<TT>::S*)r, (const St<TT>::S*)weight, (St<TT>::S*)y, hidden, eps, parts, n_parts, part_stride, sel, src_rows))
+    LADE_REQUIRE(vecs <= 4 * 1024, LADE_E_LIMIT, "%s: hidden=%d too large for the register-resident row", who, hidden);
+    bool known;
+#define RMS_LAUNCH(CH, BT)                                                                                                                           \
+    known = dispatch_dtype(dtype, [&](auto t) {                                                                                                      \
+        typedef typename Elem<decltype(t)>::S S;                                                                                                     \
+        hipLaunchKernelGGL((rmsnorm_kernel<decltype(t), ADD, CH, BT>), dim3(rows), dim3(BT), 0, st, (S*)x, (const S*)r, (const S*)weight, (S*)y, hidden, eps, parts, \
+                           n_parts, part_stride, sel, src_rows);                                                                                    \
+    })
     // one 16-byte chunk per thread up to 1024 threads - every load of the row (x, all its split-K partials, the weight) is in flight at
     // once; with two chunks per thread the store of chunk 0 into x sits between the loads of chunk 0 and chunk 1 (x may alias them), so the
     // row pays its memory latency twice: 8.7-12 us instead of 5.5-6.5 at hidden 5120 / 8192 (profiles/r5_bench_c4_kernel_medians.txt)
@@ -363,7 +347,8 @@ static int launch_rmsnorm(void* x, const void* r, const void* weight, void* y, i
     else if (vecs <= 768) { RMS_LAUNCH(1, 768); } else if (vecs <= 1024) { RMS_LAUNCH(1, 1024); } else if (vecs <= 2048) { RMS_LAUNCH(2, 1024); }
     else { RMS_LAUNCH(4, 1024); }
 #undef RMS_LAUNCH
-    return check_launch(ADD ? "lade_add_rmsnorm" : "lade_rmsnorm");
+    LADE_REQUIRE(known, LADE_E_DTYPE, "%s: unsupported dtype %d", who, dtype);
+    return check_launch(who);
 }
 
 extern "C" int lade_rmsnorm(const void* x, const void* weight, void* y, int32_t rows, int32_t hidden, float eps, int32_t dtype, void* stream) {
@@ -381,29 +366,35 @@ extern "C" int lade_embed_rmsnorm(const void* table, int32_t table_rows, const i
     return launch_rmsnorm<false>(x, table, weight, y, rows, hidden, eps, dtype, (hipStream_t)stream, nullptr, 0, 0, ids, table_rows);
 }
 
-extern "C" int lade_add_rmsnorm(void* x, const void* r, const void* weight, void* y, int32_t rows, int32_t hidden, float eps, int32_t dtype, void* stream) {
-    LADE_REQUIRE(x && r && weight && y && rows >= 0 && hidden > 0, LADE_E_ARG, "lade_add_rmsnorm: rows=%d hidden=%d", rows, hidden);
+// the residual is `r` or the n_parts fp32 split-K partials [n_parts][src rows][hidden]; sel (nullable) = the row-pruned form: x is not written
+extern "C" int lade_add_rmsnorm(void* x, const void* r, const float* parts, int32_t n_parts, int64_t part_stride, const int32_t* sel, int32_t src_rows,
+                                const void* weight, void* y, int32_t rows, int32_t hidden, float eps, int32_t dtype, void* stream) {
+    LADE_REQUIRE((r != nullptr) != (parts != nullptr), LADE_E_ARG, "lade_add_rmsnorm: exactly one of r / parts (%p, %p)", r, (const void*)parts);
+    LADE_REQUIRE(x && weight && y && rows >= 0 && hidden > 0 && (!parts || n_parts >= 1) && (!sel || src_rows > 0), LADE_E_ARG,
+                 "lade_add_rmsnorm: rows=%d hidden=%d n_parts=%d src_rows=%d", rows, hidden, n_parts, src_rows);
+    LADE_REQUIRE(!parts || dtype != LADE_F32, LADE_E_DTYPE, "lade_add_rmsnorm: split-K partials come from the 16-bit GEMM only");
     if (rows == 0) return LADE_OK;
-    hipStream_t st = (hipStream_t)stream;
-    return launch_rmsnorm<true>(x, r, weight, y, rows, hidden, eps, dtype, st);
+    return launch_rmsnorm<true>(x, r, weight, y, rows, hidden, eps, dtype, (hipStream_t)stream, parts, parts ? n_parts : 0, parts ? (size_t)part_stride : 0, sel,
+                                sel ? src_rows : 0);
 }
 
-extern "C" int lade_add_rmsnorm_rows(const void* x, const void* r, const float* parts, int32_t n_parts, int64_t part_stride, const int32_t* sel,
-                                     const void* weight, void* y, int32_t n_sel, int32_t src_rows, int32_t hidden, float eps, int32_t dtype, void* stream) {
-    LADE_REQUIRE(x && sel && weight && y && n_sel >= 0 && src_rows > 0 && hidden > 0 && ((r != nullptr) != (parts != nullptr && n_parts > 0)), LADE_E_ARG,
-                 "lade_add_rmsnorm_rows: n_sel=%d src_rows=%d hidden=%d n_parts=%d (exactly one of r / parts)", n_sel, src_rows, hidden, n_parts);
-    LADE_REQUIRE(!parts || dtype != LADE_F32, LADE_E_DTYPE, "lade_add_rmsnorm_rows: split-K partials come from the 16-bit GEMM only");
-    if (n_sel == 0) return LADE_OK;
-    return launch_rmsnorm<true>((void*)x, r, weight, y, n_sel, hidden, eps, dtype, (hipStream_t)stream, parts, n_parts, (size_t)part_stride, sel, src_rows);
-}
-
-extern "C" int lade_silu_mul(const void* gu, void* out, int32_t rows, int32_t inter, int32_t layout, int32_t dtype, void* stream) {
-    LADE_REQUIRE(gu && out && rows >= 0 && inter > 0 && (layout == 0 || (layout == 1 && inter % 16 == 0)), LADE_E_ARG, "lade_silu_mul: rows=%d inter=%d layout=%d", rows, inter, layout);
+// gu or the n_parts fp32 split-K partials [n_parts][rows][2 * inter] of the gate/up GEMM
+extern "C" int lade_silu_mul(const void* gu, const float* parts, int32_t n_parts, int64_t part_stride, void* out, int32_t rows, int32_t inter,
+                             int32_t layout, int32_t dtype, void* stream) {
+    LADE_REQUIRE((gu != nullptr) != (parts != nullptr), LADE_E_ARG, "lade_silu_mul: exactly one of gu / parts (%p, %p)", gu, (const void*)parts);
+    LADE_REQUIRE(out && rows >= 0 && inter > 0 && (layout == 0 || (layout == 1 && inter % 16 == 0)) && (!parts || (n_parts >= 1 && inter % 8 == 0)), LADE_E_ARG,
+                 "lade_silu_mul: rows=%d inter=%d layout=%d n_parts=%d", rows, inter, layout, n_parts);
+    LADE_REQUIRE(!parts || dtype != LADE_F32, LADE_E_DTYPE, "lade_silu_mul: split-K partials come from the 16-bit GEMM only");
     if (rows == 0) return LADE_OK;
     hipStream_t st = (hipStream_t)stream;
     LADE_REQUIRE(inter % 8 == 0, LADE_E_ARG, "lade_silu_mul: inter=%d must be a multiple of 8", inter);
     const int per_thr = dtype == LADE_F32 ? 4 : 8;
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(silu_mul_kernel<TT>, dim3(cdiv(inter / per_thr, 256), rows), dim3(256), 0, st, (const St<TT>::S*)gu, (St<TT>::S*)out, inter, (const float*)nullptr, 0, (size_t)0, layout));
+    const bool known = dispatch_dtype(dtype, [&](auto t) {
+        typedef typename Elem<decltype(t)>::S S;
+        hipLaunchKernelGGL(silu_mul_kernel<decltype(t)>, dim3(cdiv(inter / per_thr, 256), rows), dim3(256), 0, st, (const S*)gu, (S*)out, inter, parts,
+                           parts ? n_parts : 0, parts ? (size_t)part_stride : (size_t)0, layout);
+    });
+    LADE_REQUIRE(known, LADE_E_DTYPE, "lade_silu_mul: unsupported dtype %d", dtype);
     return check_launch("lade_silu_mul");
 }
 
@@ -421,13 +412,16 @@ extern "C" int lade_softmax_rows(const void* logits, int64_t ld, int32_t rows, i
     const int esz = dtype == LADE_F32 ? 4 : 2, nvw = 16 / esz;
     const bool vec_ok = V % nvw == 0 && V % 4 == 0 && ((uintptr_t)logits % 16) == 0 && ((size_t)ld * esz) % 16 == 0 && ((uintptr_t)probs % 16) == 0;
     const int chunks = (V / nvw + 1023) / 1024;             // 16-byte chunks per thread
-    if (vec_ok && chunks <= 8) {
-        if (chunks <= 2) { DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((softmax_rows_vec_kernel<TT, 2>), dim3(rows), dim3(1024), 0, st, (const St<TT>::S*)logits, ld, V, 1.f / temperature, probs)); }
-        else if (chunks <= 4) { DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((softmax_rows_vec_kernel<TT, 4>), dim3(rows), dim3(1024), 0, st, (const St<TT>::S*)logits, ld, V, 1.f / temperature, probs)); }
-        else { DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((softmax_rows_vec_kernel<TT, 8>), dim3(rows), dim3(1024), 0, st, (const St<TT>::S*)logits, ld, V, 1.f / temperature, probs)); }
-    } else {
-        DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(softmax_rows_kernel<TT>, dim3(rows), dim3(256), 0, st, (const St<TT>::S*)logits, ld, V, 1.f / temperature, probs));
-    }
+    const bool known = dispatch_dtype(dtype, [&](auto t) {
+        typedef decltype(t) TT;
+        const typename Elem<TT>::S* in = (const typename Elem<TT>::S*)logits;
+        const float inv_temp = 1.f / temperature;
+        if (!vec_ok || chunks > 8) hipLaunchKernelGGL(softmax_rows_kernel<TT>, dim3(rows), dim3(256), 0, st, in, ld, V, inv_temp, probs);
+        else if (chunks <= 2) hipLaunchKernelGGL((softmax_rows_vec_kernel<TT, 2>), dim3(rows), dim3(1024), 0, st, in, ld, V, inv_temp, probs);
+        else if (chunks <= 4) hipLaunchKernelGGL((softmax_rows_vec_kernel<TT, 4>), dim3(rows), dim3(1024), 0, st, in, ld, V, inv_temp, probs);
+        else hipLaunchKernelGGL((softmax_rows_vec_kernel<TT, 8>), dim3(rows), dim3(1024), 0, st, in, ld, V, inv_temp, probs);
+    });
+    LADE_REQUIRE(known, LADE_E_DTYPE, "lade_softmax_rows: unsupported dtype %d", dtype);
     return check_launch("lade_softmax_rows");
 }
 
@@ -437,28 +431,10 @@ extern "C" int lade_softmax_gather(const void* logits, int64_t ld, int32_t rows,
     LADE_REQUIRE(logits && scal && stats && rows >= 1 && V > 0 && ld >= V && temperature > 0.f && skip >= 0 && gs > 0 && g_cap >= 0 && g >= 0 && g <= g_cap &&
                      (g_cap == 0 || guess), LADE_E_ARG, "lade_softmax_gather: rows=%d V=%d T=%f g=%d gs=%d g_cap=%d", rows, V, temperature, g, gs, g_cap);
     hipStream_t st = (hipStream_t)stream;
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(softmax_gather_kernel<TT>, dim3(rows), dim3(1024), 0, st, (const St<TT>::S*)logits, ld, V, 1.f / temperature, skip,
-                                             guess, g_dev, g, gs, g_cap, scal, stats));
+    const bool known = dispatch_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(softmax_gather_kernel<decltype(t)>, dim3(rows), dim3(1024), 0, st, (const typename Elem<decltype(t)>::S*)logits, ld, V, 1.f / temperature,
+                           skip, guess, g_dev, g, gs, g_cap, scal, stats);
+    });
+    LADE_REQUIRE(known, LADE_E_DTYPE, "lade_softmax_gather: unsupported dtype %d", dtype);
     return check_launch("lade_softmax_gather");
-}
-
-// split-K aware variants: the GEMM output arrives as n_parts fp32 partials [n_parts][rows][width]
-extern "C" int lade_add_rmsnorm_parts(void* x, const float* parts, int32_t n_parts, int64_t part_stride, const void* weight, void* y,
-                                      int32_t rows, int32_t hidden, float eps, int32_t dtype, void* stream) {
-    LADE_REQUIRE(x && parts && weight && y && rows >= 0 && hidden > 0 && n_parts >= 1, LADE_E_ARG, "lade_add_rmsnorm_parts: bad args");
-    LADE_REQUIRE(dtype != LADE_F32, LADE_E_DTYPE, "lade_add_rmsnorm_parts: 16-bit dtypes only");
-    if (rows == 0) return LADE_OK;
-    return launch_rmsnorm<true>(x, nullptr, weight, y, rows, hidden, eps, dtype, (hipStream_t)stream, parts, n_parts, (size_t)part_stride);
-}
-
-extern "C" int lade_silu_mul_parts(const float* parts, int32_t n_parts, int64_t part_stride, void* out, int32_t rows, int32_t inter, int32_t layout,
-                                   int32_t dtype, void* stream) {
-    LADE_REQUIRE(parts && out && rows >= 0 && inter > 0 && inter % 8 == 0 && n_parts >= 1 && (layout == 0 || (layout == 1 && inter % 16 == 0)), LADE_E_ARG,
-                 "lade_silu_mul_parts: bad args");
-    LADE_REQUIRE(dtype != LADE_F32, LADE_E_DTYPE, "lade_silu_mul_parts: 16-bit dtypes only");
-    if (rows == 0) return LADE_OK;
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(silu_mul_kernel<TT>, dim3(cdiv(inter / 8, 256), rows), dim3(256), 0, st, (const St<TT>::S*)nullptr, (St<TT>::S*)out, inter,
-                                             parts, n_parts, (size_t)part_stride, layout));
-    return check_launch("lade_silu_mul_parts");
 }

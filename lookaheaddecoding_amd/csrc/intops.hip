@@ -696,12 +696,8 @@ extern "C" int lade_argmax_rows(const void* logits, int64_t ld, int32_t rows, in
     LADE_REQUIRE(logits && out && rows >= 0 && V > 0 && ld >= V, LADE_E_ARG, "lade_argmax_rows: rows=%d V=%d ld=%lld", rows, V, (long long)ld);
     if (rows == 0) return LADE_OK;
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case LADE_BF16: hipLaunchKernelGGL(argmax_rows_kernel<BF16>, dim3(rows), dim3(1024), 0, st, logits, ld, V, out); break;
-        case LADE_F16: hipLaunchKernelGGL(argmax_rows_kernel<F16>, dim3(rows), dim3(1024), 0, st, logits, ld, V, out); break;
-        case LADE_F32: hipLaunchKernelGGL(argmax_rows_kernel<F32>, dim3(rows), dim3(1024), 0, st, logits, ld, V, out); break;
-        default: LADE_REQUIRE(false, LADE_E_DTYPE, "lade_argmax_rows: dtype=%d", dtype);
-    }
+    const bool known = dispatch_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(argmax_rows_kernel<decltype(t)>, dim3(rows), dim3(1024), 0, st, logits, ld, V, out); });
+    LADE_REQUIRE(known, LADE_E_DTYPE, "lade_argmax_rows: dtype=%d", dtype);
     return check_launch("lade_argmax_rows");
 }
 
@@ -714,51 +710,28 @@ extern "C" int lade_argmax_pairs(const float* pairs, int32_t rows, int32_t n_blo
 
 extern "C" uint32_t lade_record_seal(const uint32_t* rec, uint32_t step_no) { return rec ? seal_words(rec, step_no) : 0u; }
 
-// EOS ids of the single-id entry points (eos < 0: none) as the set the kernels test
-static EosIds eos_one(int32_t eos) {
-    EosIds e = {};
-    e.n = eos >= 0 ? 1 : 0;
-    e.id[0] = eos;
-    return e;
-}
-
-#define POST_STEP_ARGS_OK(fn)                                                                                                              \
-    POOL_ARGS_OK(fn);                                                                                                                      \
-    LADE_REQUIRE(ctl && window && am && guess && record && W > 0 && W + N - 3 <= wcap && N >= 3 && N <= LADE_MAX_LEVEL && T_step > 0 &&   \
-                     cand_rows >= 0 && phase >= 0 && phase <= 2 && n_inp > 0 && n_inp <= wcap && (phase != 2 || n_inp == W),             \
-                 LADE_E_ARG, fn ": W=%d N=%d wcap=%d T=%d phase=%d n_inp=%d", W, N, wcap, T_step, phase, n_inp);                           \
-    LADE_REQUIRE(!pool_from_prompt || tail, LADE_E_ARG, fn ": POOL_FROM_PROMPT needs the tail buffer")
-
 extern "C" int lade_greedy_post_step(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* pool_tok, int32_t* pool_cnt, int32_t V,
                                      int32_t W, int32_t N, int32_t G, const int32_t* am, int32_t n_inp, int32_t* guess, int32_t T_step,
-                                     int32_t cand_rows, int32_t phase, int32_t pool_from_prompt, int32_t* tail, int32_t eos,
-                                     const int32_t* forced, const int32_t* level_override, int32_t* record, int32_t* record_host, void* stream) {
+                                     int32_t cand_rows, int32_t phase, int32_t pool_from_prompt, int32_t* tail, const int32_t* eos_set,
+                                     int32_t n_eos, const int32_t* forced, const int32_t* level_override, int32_t* record,
+                                     int32_t* record_host, void* stream) {
     const int gs = N - 1;
-    POST_STEP_ARGS_OK("lade_greedy_post_step");
-    // = lade_greedy_post_step_ex with a set of one id (none when eos < 0)
-    hipLaunchKernelGGL(greedy_post_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ctl, window, wcap, pool_tok, pool_cnt, V, W, N, G,
-                       am, n_inp, guess, T_step, cand_rows, phase, pool_from_prompt, tail, eos_one(eos), forced, level_override, record, record_host);
-    return check_launch("lade_greedy_post_step");
-}
-
-extern "C" int lade_greedy_post_step_ex(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* pool_tok, int32_t* pool_cnt, int32_t V,
-                                        int32_t W, int32_t N, int32_t G, const int32_t* am, int32_t n_inp, int32_t* guess, int32_t T_step,
-                                        int32_t cand_rows, int32_t phase, int32_t pool_from_prompt, int32_t* tail, const int32_t* eos_set,
-                                        int32_t n_eos, const int32_t* forced, const int32_t* level_override, int32_t* record,
-                                        int32_t* record_host, void* stream) {
-    const int gs = N - 1;
-    POST_STEP_ARGS_OK("lade_greedy_post_step_ex");
+    POOL_ARGS_OK("lade_greedy_post_step");
+    LADE_REQUIRE(ctl && window && am && guess && record && W > 0 && W + N - 3 <= wcap && N >= 3 && N <= LADE_MAX_LEVEL && T_step > 0 &&
+                     cand_rows >= 0 && phase >= 0 && phase <= 2 && n_inp > 0 && n_inp <= wcap && (phase != 2 || n_inp == W),
+                 LADE_E_ARG, "lade_greedy_post_step: W=%d N=%d wcap=%d T=%d phase=%d n_inp=%d", W, N, wcap, T_step, phase, n_inp);
+    LADE_REQUIRE(!pool_from_prompt || tail, LADE_E_ARG, "lade_greedy_post_step: POOL_FROM_PROMPT needs the tail buffer");
     LADE_REQUIRE(n_eos >= 0 && n_eos <= LADE_GEN_MAX_EOS && (n_eos == 0 || eos_set), LADE_E_ARG,
-                 "lade_greedy_post_step_ex: n_eos=%d (0..%d, eos_set needed when > 0)", n_eos, LADE_GEN_MAX_EOS);
+                 "lade_greedy_post_step: n_eos=%d (0..%d, eos_set needed when > 0)", n_eos, LADE_GEN_MAX_EOS);
     EosIds eos = {};
     eos.n = n_eos;
     for (int e = 0; e < n_eos; ++e) {
-        LADE_REQUIRE(eos_set[e] >= 0, LADE_E_ARG, "lade_greedy_post_step_ex: eos_set[%d]=%d is negative", e, eos_set[e]);
+        LADE_REQUIRE(eos_set[e] >= 0, LADE_E_ARG, "lade_greedy_post_step: eos_set[%d]=%d is negative", e, eos_set[e]);
         eos.id[e] = eos_set[e];
     }
     hipLaunchKernelGGL(greedy_post_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ctl, window, wcap, pool_tok, pool_cnt, V, W, N, G,
                        am, n_inp, guess, T_step, cand_rows, phase, pool_from_prompt, tail, eos, forced, level_override, record, record_host);
-    return check_launch("lade_greedy_post_step_ex");
+    return check_launch("lade_greedy_post_step");
 }
 
 extern "C" int lade_lp_pack(const int32_t* am_out, const int32_t* am_inp, int32_t n_inp, const int32_t* am_guess, int32_t g_local,
@@ -783,6 +756,6 @@ extern "C" int lade_lp_reduce_apply(const int32_t* all_rec, int32_t R, int32_t r
     LADE_REQUIRE(all_rec && ctl && window && guess_all && scratch && record && R > 0 && rec_words >= 4 + split && W <= wcap && N >= 3 && N <= LADE_MAX_LEVEL,
                  LADE_E_ARG, "lade_lp_reduce_apply: R=%d rec_words=%d split=%d", R, rec_words, split);
     hipLaunchKernelGGL(lp_reduce_apply_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, all_rec, R, rec_words, split, ctl, window, wcap,
-                       pool_tok, pool_cnt, V, W, N, G, phase, guess_all, scratch, record, pool_from_prompt, tail, eos_one(eos));
+                       pool_tok, pool_cnt, V, W, N, G, phase, guess_all, scratch, record, pool_from_prompt, tail, EosIds{eos >= 0 ? 1 : 0, {eos}});
     return check_launch("lade_lp_reduce_apply");
 }

@@ -313,8 +313,7 @@ __global__ __launch_bounds__(256) void kv_pack_bshd_kernel(const S* k, const S* 
 template <typename T>
 static int launch_rope(void* qkv, const int32_t* positions, const void* cos_tab, const void* sin_tab, void* k_cache,
                        void* vt_cache, int T_, int P, const int32_t* dyn_P, int H, int Hkv, int d, int S_max, int max_pos,
-                       hipStream_t st, const float* parts = nullptr, int n_parts = 0, size_t part_stride = 0, void* q_out = nullptr,
-                       const lade_qkv_epilogue* epi = nullptr) {
+                       hipStream_t st, const float* parts, int n_parts, size_t part_stride, void* q_out, const lade_qkv_epilogue* epi) {
     typedef typename Elem<T>::S S;
     const int n_vblk = Hkv * cdiv(T_, 64) * cdiv(d, 32);
     // one 16-byte pair item per thread: blocks per token = items / 256 (latency bound: more, smaller work-groups)
@@ -377,28 +376,42 @@ extern "C" int lade_rope_rows_dynamic(const int32_t* positions, int32_t T, int32
     LADE_REQUIRE(positions && state && inv_tab && cos_rows && sin_rows && T > 0 && P >= 0 && n_len > 0 && max_position_embeddings > 0 && d > 0 && d % 2 == 0 &&
                      d <= 256, LADE_E_ARG, "lade_rope_rows_dynamic: T=%d P=%d n_len=%d d=%d", T, P, n_len, d);
     hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case LADE_BF16: hipLaunchKernelGGL(rope_rows_dynamic_kernel<BF16>, dim3(T), dim3(128), 0, st, positions, T, P, dyn_P, len_hint, state, max_position_embeddings, inv_tab, n_len, d, (uint16_t*)cos_rows, (uint16_t*)sin_rows, g_dev, gcap, gs); break;
-        case LADE_F16: hipLaunchKernelGGL(rope_rows_dynamic_kernel<F16>, dim3(T), dim3(128), 0, st, positions, T, P, dyn_P, len_hint, state, max_position_embeddings, inv_tab, n_len, d, (uint16_t*)cos_rows, (uint16_t*)sin_rows, g_dev, gcap, gs); break;
-        case LADE_F32: hipLaunchKernelGGL(rope_rows_dynamic_kernel<F32>, dim3(T), dim3(128), 0, st, positions, T, P, dyn_P, len_hint, state, max_position_embeddings, inv_tab, n_len, d, (float*)cos_rows, (float*)sin_rows, g_dev, gcap, gs); break;
-        default: LADE_REQUIRE(false, LADE_E_DTYPE, "lade_rope_rows_dynamic: dtype=%d", dtype);
-    }
+    const bool known = dispatch_dtype(dtype, [&](auto t) {
+        typedef typename Elem<decltype(t)>::S S;
+        hipLaunchKernelGGL(rope_rows_dynamic_kernel<decltype(t)>, dim3(T), dim3(128), 0, st, positions, T, P, dyn_P, len_hint, state, max_position_embeddings,
+                           inv_tab, n_len, d, (S*)cos_rows, (S*)sin_rows, g_dev, gcap, gs);
+    });
+    LADE_REQUIRE(known, LADE_E_DTYPE, "lade_rope_rows_dynamic: dtype=%d", dtype);
     return check_launch("lade_rope_rows_dynamic");
 }
 
-extern "C" int lade_rope_kv_append(void* qkv, const int32_t* positions, const void* cos_tab, const void* sin_tab,
-                                   void* k_cache, void* vt_cache, int32_t T, int32_t P, const int32_t* dyn_P, int32_t H,
-                                   int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype, void* stream) {
-    LADE_REQUIRE(qkv && positions && cos_tab && sin_tab && k_cache && vt_cache, LADE_E_ARG, "lade_rope_kv_append: null pointer");
-    LADE_REQUIRE(T > 0 && P >= 0 && P + T <= S_max && H > 0 && Hkv > 0 && d > 0 && d % 2 == 0 && d <= 256 && max_pos > 0,
+// RoPE + KV append from either source of qkv: the materialised projection (q rotated in place) or n_parts fp32 split-K partials
+// [n_parts][T][(H+2Hkv)*d] (the rotated q goes to q_out [T][H*d]); `epi` (nullable) is the qkv epilogue of lade_qkv_epilogue
+extern "C" int lade_rope_kv_append(void* qkv, const float* parts, int32_t n_parts, int64_t part_stride, void* q_out, const int32_t* positions,
+                                   const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int32_t T, int32_t P,
+                                   const int32_t* dyn_P, int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
+                                   const lade_qkv_epilogue* epi, void* stream) {
+    LADE_REQUIRE((qkv != nullptr) != (parts != nullptr), LADE_E_ARG, "lade_rope_kv_append: exactly one of qkv / parts (%p, %p)", qkv, (const void*)parts);
+    LADE_REQUIRE(positions && cos_tab && sin_tab && k_cache && vt_cache && (!parts || (q_out && n_parts >= 1)), LADE_E_ARG,
+                 "lade_rope_kv_append: null pointer (the partials need q_out and n_parts >= 1: n_parts=%d)", n_parts);
+    // the partials are read on the 16-byte path only
+    LADE_REQUIRE(T > 0 && P >= 0 && P + T <= S_max && H > 0 && Hkv > 0 && d > 0 && (parts ? (d / 2) % 8 == 0 : d % 2 == 0) && d <= 256 && max_pos > 0,
                  LADE_E_ARG, "lade_rope_kv_append: T=%d P=%d S_max=%d H=%d Hkv=%d d=%d", T, P, S_max, H, Hkv, d);
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case LADE_BF16: return launch_rope<BF16>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st);
-        case LADE_F16: return launch_rope<F16>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st);
-        case LADE_F32: return launch_rope<F32>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st);
-    }
-    LADE_REQUIRE(false, LADE_E_DTYPE, "lade_rope_kv_append: dtype=%d", dtype);
+    const bool has_epi = epi && (epi->bias || epi->q_norm || epi->k_norm), norm = has_epi && (epi->q_norm || epi->k_norm);
+    LADE_REQUIRE(!has_epi || ((uintptr_t)epi->bias | (uintptr_t)epi->q_norm | (uintptr_t)epi->k_norm) % 16 == 0, LADE_E_ARG,
+                 "lade_rope_kv_append: bias / q_norm / k_norm must be 16-byte aligned (%p %p %p)", epi->bias, epi->q_norm, epi->k_norm);
+    LADE_REQUIRE(!norm || (epi->eps >= 0.f && epi->eps < 1.f), LADE_E_ARG, "lade_rope_kv_append: eps=%g", (double)epi->eps);
+    // ... so the head norm's lane reduction needs the d/16 lanes of a head to be a power of two there
+    LADE_REQUIRE(!(parts && norm) || ((d / 16) & (d / 16 - 1)) == 0, LADE_E_ARG,
+                 "lade_rope_kv_append: the head norm on partials needs d / 16 to be a power of two (d=%d)", d);
+    LADE_REQUIRE(!parts || dtype != LADE_F32, LADE_E_DTYPE, "lade_rope_kv_append: split-K partials come from the 16-bit GEMM only");
+    int rc = LADE_OK;
+    const bool known = dispatch_dtype(dtype, [&](auto t) {
+        rc = launch_rope<decltype(t)>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, (hipStream_t)stream, parts,
+                                      parts ? n_parts : 0, parts ? (size_t)part_stride : 0, parts ? q_out : nullptr, epi);
+    });
+    LADE_REQUIRE(known, LADE_E_DTYPE, "lade_rope_kv_append: dtype=%d", dtype);
+    return rc;
 }
 
 extern "C" int lade_kv_commit(void* cache, int64_t layer_stride, int64_t v_offset, int32_t L, int32_t Hkv, int32_t d,
@@ -443,69 +456,4 @@ extern "C" int lade_kv_pack_bshd(const void* k, const void* v, int64_t tok_strid
         hipLaunchKernelGGL(kv_pack_bshd_kernel<uint32_t>, grid, dim3(256), lds, st, (const uint32_t*)k, (const uint32_t*)v, (uint32_t*)k_cache, (uint32_t*)vt_cache, S, Hkv, d, S_max, tok_stride, head_stride);
     }
     return check_launch("lade_kv_pack_bshd");
-}
-
-// qkv arrives as n_parts fp32 split-K partials [n_parts][T][(H+2Hkv)*d]; the rotated q goes to q_out [T][H*d]
-extern "C" int lade_rope_kv_append_parts(const float* parts, int32_t n_parts, int64_t part_stride, void* q_out, const int32_t* positions,
-                                         const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int32_t T, int32_t P,
-                                         const int32_t* dyn_P, int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
-                                         void* stream) {
-    LADE_REQUIRE(parts && q_out && positions && cos_tab && sin_tab && k_cache && vt_cache && n_parts >= 1, LADE_E_ARG, "lade_rope_kv_append_parts: null pointer");
-    LADE_REQUIRE(T > 0 && P >= 0 && P + T <= S_max && H > 0 && Hkv > 0 && d > 0 && (d / 2) % 8 == 0 && d <= 256 && max_pos > 0,
-                 LADE_E_ARG, "lade_rope_kv_append_parts: T=%d P=%d S_max=%d H=%d Hkv=%d d=%d", T, P, S_max, H, Hkv, d);
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case LADE_BF16: return launch_rope<BF16>(nullptr, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, parts, n_parts, (size_t)part_stride, q_out);
-        case LADE_F16: return launch_rope<F16>(nullptr, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, parts, n_parts, (size_t)part_stride, q_out);
-    }
-    LADE_REQUIRE(false, LADE_E_DTYPE, "lade_rope_kv_append_parts: dtype=%d", dtype);
-}
-
-// ---- the qkv epilogue (lade_qkv_epilogue): the two entry points above plus bias / per-head RMSNorm of q and k ----
-static int check_epilogue(const lade_qkv_epilogue* epi, int32_t dtype, const char* who) {
-    if (!epi || !(epi->bias || epi->q_norm || epi->k_norm)) return LADE_OK;
-    LADE_REQUIRE(((uintptr_t)epi->bias | (uintptr_t)epi->q_norm | (uintptr_t)epi->k_norm) % 16 == 0, LADE_E_ARG,
-                 "%s: bias / q_norm / k_norm must be 16-byte aligned (%p %p %p)", who, epi->bias, epi->q_norm, epi->k_norm);
-    LADE_REQUIRE(!(epi->q_norm || epi->k_norm) || (epi->eps >= 0.f && epi->eps < 1.f), LADE_E_ARG, "%s: eps=%g", who, (double)epi->eps);
-    (void)dtype;
-    return LADE_OK;
-}
-
-extern "C" int lade_rope_kv_append_ex(void* qkv, const int32_t* positions, const void* cos_tab, const void* sin_tab,
-                                      void* k_cache, void* vt_cache, int32_t T, int32_t P, const int32_t* dyn_P, int32_t H,
-                                      int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
-                                      const lade_qkv_epilogue* epi, void* stream) {
-    LADE_REQUIRE(qkv && positions && cos_tab && sin_tab && k_cache && vt_cache, LADE_E_ARG, "lade_rope_kv_append_ex: null pointer");
-    LADE_REQUIRE(T > 0 && P >= 0 && P + T <= S_max && H > 0 && Hkv > 0 && d > 0 && d % 2 == 0 && d <= 256 && max_pos > 0,
-                 LADE_E_ARG, "lade_rope_kv_append_ex: T=%d P=%d S_max=%d H=%d Hkv=%d d=%d", T, P, S_max, H, Hkv, d);
-    const int rc = check_epilogue(epi, dtype, "lade_rope_kv_append_ex");
-    if (rc != LADE_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case LADE_BF16: return launch_rope<BF16>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, nullptr, 0, 0, nullptr, epi);
-        case LADE_F16: return launch_rope<F16>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, nullptr, 0, 0, nullptr, epi);
-        case LADE_F32: return launch_rope<F32>(qkv, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, nullptr, 0, 0, nullptr, epi);
-    }
-    LADE_REQUIRE(false, LADE_E_DTYPE, "lade_rope_kv_append_ex: dtype=%d", dtype);
-}
-
-extern "C" int lade_rope_kv_append_parts_ex(const float* parts, int32_t n_parts, int64_t part_stride, void* q_out, const int32_t* positions,
-                                            const void* cos_tab, const void* sin_tab, void* k_cache, void* vt_cache, int32_t T, int32_t P,
-                                            const int32_t* dyn_P, int32_t H, int32_t Hkv, int32_t d, int32_t S_max, int32_t max_pos, int32_t dtype,
-                                            const lade_qkv_epilogue* epi, void* stream) {
-    LADE_REQUIRE(parts && q_out && positions && cos_tab && sin_tab && k_cache && vt_cache && n_parts >= 1, LADE_E_ARG, "lade_rope_kv_append_parts_ex: null pointer");
-    LADE_REQUIRE(T > 0 && P >= 0 && P + T <= S_max && H > 0 && Hkv > 0 && d > 0 && (d / 2) % 8 == 0 && d <= 256 && max_pos > 0,
-                 LADE_E_ARG, "lade_rope_kv_append_parts_ex: T=%d P=%d S_max=%d H=%d Hkv=%d d=%d", T, P, S_max, H, Hkv, d);
-    const int rc = check_epilogue(epi, dtype, "lade_rope_kv_append_parts_ex");
-    if (rc != LADE_OK) return rc;
-    // the partials are read on the 16-byte path only: the head norm's lane reduction needs the d/16 lanes of a head to be a power of two
-    const int vph = d / 16;
-    LADE_REQUIRE(!(epi && (epi->q_norm || epi->k_norm)) || (vph & (vph - 1)) == 0, LADE_E_ARG,
-                 "lade_rope_kv_append_parts_ex: the head norm needs d / 16 to be a power of two (d=%d)", d);
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case LADE_BF16: return launch_rope<BF16>(nullptr, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, parts, n_parts, (size_t)part_stride, q_out, epi);
-        case LADE_F16: return launch_rope<F16>(nullptr, positions, cos_tab, sin_tab, k_cache, vt_cache, T, P, dyn_P, H, Hkv, d, S_max, max_pos, st, parts, n_parts, (size_t)part_stride, q_out, epi);
-    }
-    LADE_REQUIRE(false, LADE_E_DTYPE, "lade_rope_kv_append_parts_ex: dtype=%d", dtype);
 }

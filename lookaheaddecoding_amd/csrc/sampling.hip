@@ -42,10 +42,6 @@ __device__ __forceinline__ uint32_t float_key(float x) {        // ascending flo
 }
 __device__ __forceinline__ float key_float(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
-template <typename T> __device__ __forceinline__ float load_logit(const void* p, size_t i);
-template <> __device__ __forceinline__ float load_logit<F32>(const void* p, size_t i) { return reinterpret_cast<const float*>(p)[i]; }
-template <> __device__ __forceinline__ float load_logit<BF16>(const void* p, size_t i) { return to_f32<BF16>(reinterpret_cast<const uint16_t*>(p)[i]); }
-template <> __device__ __forceinline__ float load_logit<F16>(const void* p, size_t i) { return to_f32<F16>(reinterpret_cast<const uint16_t*>(p)[i]); }
 
 // Work-group reductions (every thread gets the result).  `red` holds 2 x WARP_WAVES slots used alternately (`turn` flips per call): the
 // writes of call n+1 go to the other half, and a wave can only reach call n+2 through the barrier of call n+1 - one barrier per call.
@@ -128,7 +124,7 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_rows_kernel(const void* log
         const int i = i0 + e;
         uint32_t k = 0u;
         if (i < V) {
-            float v = load_logit<T>(logits, (size_t)prow * ld + i);
+            float v = Elem<T>::ld(static_cast<const typename Elem<T>::S*>(logits)[(size_t)prow * ld + i]);
             if (temperature != 1.0f) v = v / temperature;
             k = float_key(v);
         }
@@ -302,7 +298,7 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_rows_big_kernel(const void*
             const int i = 4 * q + e;
             k[e] = 0u;
             if (i < V) {
-                float v = load_logit<T>(logits, (size_t)prow * ld + i);
+                float v = Elem<T>::ld(static_cast<const typename Elem<T>::S*>(logits)[(size_t)prow * ld + i]);
                 if (temperature != 1.0f) v = v / temperature;
                 k[e] = float_key(v);
                 kmax = k[e] > kmax ? k[e] : kmax;
@@ -557,10 +553,8 @@ static int warp_rows_checked(const char* who, const void* logits, int64_t ld, in
     LADE_REQUIRE(V <= (1 << 24), LADE_E_LIMIT, "%s: V=%d > %d", who, V, 1 << 24);
     if (rows == 0) return LADE_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == LADE_F32) launch_warp_rows<F32>(logits, ld, rows, V, p, skip, out, st);
-    else if (dtype == LADE_BF16) launch_warp_rows<BF16>(logits, ld, rows, V, p, skip, out, st);
-    else if (dtype == LADE_F16) launch_warp_rows<F16>(logits, ld, rows, V, p, skip, out, st);
-    else LADE_REQUIRE(false, LADE_E_DTYPE, "%s: dtype=%d", who, dtype);
+    const bool known = dispatch_dtype(dtype, [&](auto t) { launch_warp_rows<decltype(t)>(logits, ld, rows, V, p, skip, out, st); });
+    LADE_REQUIRE(known, LADE_E_DTYPE, "%s: dtype=%d", who, dtype);
     return check_launch(who);
 }
 

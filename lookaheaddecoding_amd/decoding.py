@@ -269,7 +269,7 @@ class LookaheadDecoder:
             raise cabi.LadeHipError(f"W={W} N={N} G={G} needs {self.max_step_tokens()} tokens per step > engine.max_T={engine.max_T}")
         # host state of the current run (start / sample_start)
         self.prompt, self.window0, self.tokens = [], [], []
-        self.eos_set, self.eos, self.controls = (), -1, None
+        self.eos_set, self._eos_host, self.controls = (), ops.host_ids(()), None
         self.steps, self.P, self.g, self.fill_level = 0, 0, 0, 0
         self.finished_by_eos = False
         self._s = None                    # the sampling run's warper, RNGs and forced-hits buffers (sample_start)
@@ -327,7 +327,7 @@ class LookaheadDecoder:
             pt = torch.tensor(self.prompt, dtype=torch.int32, device=e.device)
             call("lade_pool_fill_prompt", ptr(st.pool_tok), ptr(st.pool_cnt), st.V, G, gs, ptr(pt), len(self.prompt))
         self.eos_set = eos_set(eos_token_id)
-        self.eos = self.eos_set[0] if self.eos_set else -1
+        self._eos_host = ops.host_ids(self.eos_set)            # what every post-step of the run passes: built once, not per step
         self.controls = controls if controls is not None and controls.active else None
         if self.controls is not None:
             if self._gen is None:
@@ -370,16 +370,11 @@ class LookaheadDecoder:
         return out
 
     def _post_step(self, am, n_inp: int, T: int, cand_rows: int, phase: int, forced=None, level_override=None, record_host=None) -> None:
-        """The fused post-step (+ the seen-set update under controls).  At most one EOS id and no controls: lade_greedy_post_step, the
-        plain step's launch; otherwise lade_greedy_post_step_ex with the whole EOS set."""
-        e, st = self.e, self.st
-        head = (ptr(st.ctl), ptr(st.window), st.wcap, ptr(st.pool_tok), ptr(st.pool_cnt), st.V, self.W, self.N, self.G, ptr(am), n_inp,
-                ptr(st.guess), T, cand_rows, phase, int(self.pool_from_prompt), ptr(st.tail))
-        tail = (ptr(forced), ptr(level_override), ptr(st.record), ptr(record_host))
-        if self.controls is None and len(self.eos_set) <= 1:
-            call("lade_greedy_post_step", *head, self.eos, *tail)
-        else:
-            call("lade_greedy_post_step_ex", *head, ops.host_ids(self.eos_set), len(self.eos_set), *tail)
+        """The fused post-step with the run's EOS set (+ the seen-set update under controls)."""
+        st = self.st
+        call("lade_greedy_post_step", ptr(st.ctl), ptr(st.window), st.wcap, ptr(st.pool_tok), ptr(st.pool_cnt), st.V, self.W, self.N, self.G, ptr(am), n_inp,
+             ptr(st.guess), T, cand_rows, phase, int(self.pool_from_prompt), ptr(st.tail), self._eos_host, len(self.eos_set), ptr(forced),
+             ptr(level_override), ptr(st.record), ptr(record_host))
         if self.controls is not None:
             ops.gen_ctl_update(self._gen, st.ctl)
 

@@ -220,7 +220,7 @@ class StepEngine(KernelDecisions):
 
     def _fuse_gate_up(self, wg: torch.Tensor, wu: torch.Tensor) -> torch.Tensor:
         """gate and up projections as ONE weight.  16-row interleaved ([16 gate rows | their 16 up rows] per 32-row MFMA tile) so that
-        the GEMM's SwiGLU epilogue is lane-local; every consumer of the fused output (lade_silu_mul*, layout 1) knows the order.
+        the GEMM's SwiGLU epilogue is lane-local; every consumer of the fused output (lade_silu_mul, layout 1) knows the order.
         Shapes whose intermediate size is not a multiple of 16 keep the plain [gate | up] concatenation (layout 0)."""
         self.gu_layout = 1 if wg.shape[0] % 16 == 0 else 0
         return ops.interleave_gate_up(wg, wu) if self.gu_layout else torch.cat([wg, wu], dim=0).contiguous()
@@ -482,21 +482,15 @@ class StepEngine(KernelDecisions):
                 cfg_qkv.gemm_parts(h, self._w(lw, "wqkv"), part)
                 qb = self.ws_q[:T]
                 if self.skip_attn != "all":
-                    if lw["epi_parts"] is not None:
-                        ops.rope_kv_append_parts_ex(part, cfg_qkv.n_split, qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d,
-                                                    dyn_P=dyn_P, epi=lw["epi_parts"])
-                    else:
-                        ops.rope_kv_append_parts(part, cfg_qkv.n_split, qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P)
+                    ops.rope_kv_append_parts(part, cfg_qkv.n_split, qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), T, P, H=H, Hkv=Hkv, d=d,
+                                             dyn_P=dyn_P, epi=lw["epi_parts"])
                 q_in = qb
             else:
                 if "bqkv" in lw:                  # F.linear with a bias: one rounding of (h W^T + b)
                     torch.addmm(lw["bqkv"], h, self._row(lw, "wqkv").t(), out=qkv)
                 else:
                     torch.matmul(h, self._row(lw, "wqkv").t(), out=qkv)
-                if lw["epi_lib"] is not None:
-                    ops.rope_kv_append_ex(qkv, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P, epi=lw["epi_lib"])
-                else:
-                    ops.rope_kv_append(qkv, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P)
+                ops.rope_kv_append(qkv, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), P, H=H, Hkv=Hkv, d=d, dyn_P=dyn_P, epi=lw["epi_lib"])
                 q_in = qkv
             ev = None if self.skip_attn else self.attn_events      # skip_attn: `o` keeps stale values, the logits are meaningless
             if ev is not None:              # bench.py: hipEvents around the attention launch pair, in the real step

@@ -186,18 +186,6 @@ def mask_render(mask: StepMask, device="cuda") -> torch.Tensor:
     return out
 
 
-def rope_kv_append(qkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
-                   vt_cache: torch.Tensor, P: int, *, H: int, Hkv: int, d: int, dyn_P: Optional[torch.Tensor] = None) -> None:
-    """qkv [T, (H+2Hkv)*d] (q rotated in place); k_cache [Hkv,S_max,d]; vt_cache [Hkv,d,S_max]."""
-    _dev(qkv, "qkv")
-    T = qkv.shape[0]
-    assert qkv.is_contiguous() and qkv.shape[1] == (H + 2 * Hkv) * d
-    assert positions.dtype == torch.int32 and positions.numel() >= T
-    assert cos.dtype == qkv.dtype and cos.shape[1] == d and cos.is_contiguous() and sin.is_contiguous()
-    call("lade_rope_kv_append", ptr(qkv), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache), ptr(vt_cache), T, P, ptr(dyn_P), H, Hkv,
-         d, k_cache.shape[1], cos.shape[0], dtype_code(qkv))
-
-
 def qkv_epilogue(bias: Optional[torch.Tensor] = None, q_norm: Optional[torch.Tensor] = None, k_norm: Optional[torch.Tensor] = None,
                  eps: float = 1e-6) -> cabi.QkvEpilogue:
     """lade_qkv_epilogue over device tensors in the model dtype: bias [(H+2Hkv)*d] (Qwen2's q / k / v bias, fused like wqkv), q_norm / k_norm [d]
@@ -210,17 +198,24 @@ def qkv_epilogue(bias: Optional[torch.Tensor] = None, q_norm: Optional[torch.Ten
     return cabi.QkvEpilogue(ptr(bias), ptr(q_norm), ptr(k_norm), float(eps))
 
 
-def rope_kv_append_ex(qkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
-                      vt_cache: torch.Tensor, P: int, *, H: int, Hkv: int, d: int, dyn_P: Optional[torch.Tensor] = None,
-                      epi: Optional[cabi.QkvEpilogue] = None) -> None:
-    """rope_kv_append with the qkv epilogue (`qkv_epilogue`; None = the plain kernel)."""
+def _rope_kv_append(qkv, part, n_parts, q_out, positions, cos, sin, k_cache, vt_cache, T, P, H, Hkv, d, dyn_P, epi) -> None:
+    """the one call behind both RoPE wrappers: exactly one of qkv / part"""
+    call("lade_rope_kv_append", ptr(qkv), ptr(part), n_parts, T * (H + 2 * Hkv) * d, ptr(q_out), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache),
+         ptr(vt_cache), T, P, ptr(dyn_P), H, Hkv, d, k_cache.shape[1], cos.shape[0], dtype_code(q_out if qkv is None else qkv),
+         None if epi is None else C.byref(epi))
+
+
+def rope_kv_append(qkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
+                   vt_cache: torch.Tensor, P: int, *, H: int, Hkv: int, d: int, dyn_P: Optional[torch.Tensor] = None,
+                   epi: Optional[cabi.QkvEpilogue] = None) -> None:
+    """qkv [T, (H+2Hkv)*d] (q rotated in place); k_cache [Hkv,S_max,d]; vt_cache [Hkv,d,S_max]; epi: the qkv epilogue (`qkv_epilogue`; None =
+    the plain kernel)."""
     _dev(qkv, "qkv")
     T = qkv.shape[0]
     assert qkv.is_contiguous() and qkv.shape[1] == (H + 2 * Hkv) * d
     assert positions.dtype == torch.int32 and positions.numel() >= T
     assert cos.dtype == qkv.dtype and cos.shape[1] == d and cos.is_contiguous() and sin.is_contiguous()
-    call("lade_rope_kv_append_ex", ptr(qkv), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache), ptr(vt_cache), T, P, ptr(dyn_P), H, Hkv,
-         d, k_cache.shape[1], cos.shape[0], dtype_code(qkv), None if epi is None else C.byref(epi))
+    _rope_kv_append(qkv, None, 0, None, positions, cos, sin, k_cache, vt_cache, T, P, H, Hkv, d, dyn_P, epi)
 
 
 def kv_commit(cache: torch.Tensor, src: int, dst: int, cnt: int, ctl: Optional[torch.Tensor] = None) -> None:
@@ -261,7 +256,7 @@ def add_rmsnorm(x: torch.Tensor, r: torch.Tensor, w: torch.Tensor, eps: float, o
     assert x.is_contiguous() and r.is_contiguous() and x.shape == r.shape
     if out is None:
         out = torch.empty_like(x)
-    call("lade_add_rmsnorm", ptr(x), ptr(r), ptr(w), ptr(out), x.shape[0], x.shape[1], eps, dtype_code(x))
+    call("lade_add_rmsnorm", ptr(x), ptr(r), None, 0, 0, None, 0, ptr(w), ptr(out), x.shape[0], x.shape[1], eps, dtype_code(x))
     return out
 
 
@@ -273,8 +268,7 @@ def add_rmsnorm_rows(x: torch.Tensor, sel: torch.Tensor, n_sel: int, w: torch.Te
     assert x.is_contiguous() and sel.dtype == torch.int32 and (r is None) != (part is None)
     if out is None:
         out = torch.empty(n_sel, hidden, dtype=x.dtype, device=x.device)
-    call("lade_add_rmsnorm_rows", ptr(x), ptr(r), ptr(part), n_parts if part is not None else 0, rows * hidden, ptr(sel), ptr(w), ptr(out), n_sel, rows, hidden,
-         eps, dtype_code(x))
+    call("lade_add_rmsnorm", ptr(x), ptr(r), ptr(part), n_parts, rows * hidden, ptr(sel), rows, ptr(w), ptr(out), n_sel, hidden, eps, dtype_code(x))
     return out[:n_sel]
 
 
@@ -284,7 +278,7 @@ def silu_mul(gu: torch.Tensor, out: Optional[torch.Tensor] = None, layout: int =
     inter = gu.shape[1] // 2
     if out is None:
         out = torch.empty(gu.shape[0], inter, dtype=gu.dtype, device=gu.device)
-    call("lade_silu_mul", ptr(gu), ptr(out), gu.shape[0], inter, layout, dtype_code(gu))
+    call("lade_silu_mul", ptr(gu), None, 0, 0, ptr(out), gu.shape[0], inter, layout, dtype_code(gu))
     return out
 
 
@@ -456,29 +450,29 @@ def gemm_parts(a: torch.Tensor, w: torch.Tensor, part: torch.Tensor, n_split: in
 
 
 def add_rmsnorm_parts(x: torch.Tensor, part: torch.Tensor, n_parts: int, w: torch.Tensor, eps: float, out: torch.Tensor) -> torch.Tensor:
+    """add_rmsnorm with the residual as the first n_parts fp32 split-K partials of `part` ([n_parts][rows][hidden])"""
     rows, hidden = x.shape
-    call("lade_add_rmsnorm_parts", ptr(x), ptr(part), n_parts, rows * hidden, ptr(w), ptr(out), rows, hidden, eps, dtype_code(x))
+    call("lade_add_rmsnorm", ptr(x), None, ptr(part), n_parts, rows * hidden, None, 0, ptr(w), ptr(out), rows, hidden, eps, dtype_code(x))
     return out
 
 
 def silu_mul_parts(part: torch.Tensor, n_parts: int, rows: int, inter: int, out: torch.Tensor, layout: int = 0) -> torch.Tensor:
-    call("lade_silu_mul_parts", ptr(part), n_parts, rows * 2 * inter, ptr(out), rows, inter, layout, dtype_code(out))
+    """silu_mul on the first n_parts fp32 split-K partials of `part` ([n_parts][rows][2 * inter])"""
+    call("lade_silu_mul", None, ptr(part), n_parts, rows * 2 * inter, ptr(out), rows, inter, layout, dtype_code(out))
     return out
 
 
 def rope_kv_append_parts(part: torch.Tensor, n_parts: int, q_out: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
                          k_cache: torch.Tensor, vt_cache: torch.Tensor, T: int, P: int, *, H: int, Hkv: int, d: int,
-                         dyn_P: Optional[torch.Tensor] = None) -> None:
-    call("lade_rope_kv_append_parts", ptr(part), n_parts, T * (H + 2 * Hkv) * d, ptr(q_out), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache),
-         ptr(vt_cache), T, P, ptr(dyn_P), H, Hkv, d, k_cache.shape[1], cos.shape[0], dtype_code(q_out))
+                         dyn_P: Optional[torch.Tensor] = None, epi: Optional[cabi.QkvEpilogue] = None) -> None:
+    """rope_kv_append on the first n_parts fp32 split-K partials of `part` ([n_parts][T][(H+2Hkv)*d]); the rotated q goes to q_out [T, H*d].
+    The epilogue's bias joins the fp32 sum of the partials before its one rounding."""
+    _rope_kv_append(None, part, n_parts, q_out, positions, cos, sin, k_cache, vt_cache, T, P, H, Hkv, d, dyn_P, epi)
 
 
-def rope_kv_append_parts_ex(part: torch.Tensor, n_parts: int, q_out: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-                            k_cache: torch.Tensor, vt_cache: torch.Tensor, T: int, P: int, *, H: int, Hkv: int, d: int,
-                            dyn_P: Optional[torch.Tensor] = None, epi: Optional[cabi.QkvEpilogue] = None) -> None:
-    """rope_kv_append_parts with the qkv epilogue: the bias joins the fp32 sum of the partials before its one rounding"""
-    call("lade_rope_kv_append_parts_ex", ptr(part), n_parts, T * (H + 2 * Hkv) * d, ptr(q_out), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache),
-         ptr(vt_cache), T, P, ptr(dyn_P), H, Hkv, d, k_cache.shape[1], cos.shape[0], dtype_code(q_out), None if epi is None else C.byref(epi))
+# the names the epilogue arrived under: the same two functions (tests/test_gpu_qkv_epilogue.py compares `x(..)` with `x_ex(.., epi=None)`)
+rope_kv_append_ex = rope_kv_append
+rope_kv_append_parts_ex = rope_kv_append_parts
 
 
 # ---- generation controls (repetition penalty, min length; include/lade_hip.h "generation controls") -------------------------------

@@ -32,7 +32,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
         assert hasattr(lib, s), f"{s} declared in lade_hip.h but not exported"
         assert s in cabi.SIGNATURES, f"{s} has no ctypes signature"
     assert sorted(cabi.SIGNATURES) == syms
-    assert lib.lade_version() == cabi.ABI_VERSION == 4
+    assert lib.lade_version() == cabi.ABI_VERSION == 5
 
 
 def test_attn_args_has_the_size_the_library_was_compiled_with():
@@ -55,6 +55,32 @@ def test_argument_validation_returns_error_codes_not_crashes(lib):
     assert rc == -1
     rc = lib.lade_pool_lookup(None, None, 10, 0, 3, None, None, None, None)
     assert rc == -1 and b"lade_pool_lookup" in lib.lade_last_error_string()
+
+
+def test_merged_entry_points_take_exactly_one_source(lib):
+    """lade_rope_kv_append (qkv | parts), lade_add_rmsnorm (r | parts) and lade_silu_mul (gu | parts): both sources or neither is LADE_E_ARG
+    with the function's name, before any launch (dummy non-null pointers, no GPU)"""
+    from lookaheaddecoding_amd import cabi
+    p = 1 << 20
+    for qkv, parts in ((p, p), (None, None)):
+        rc = lib.lade_rope_kv_append(qkv, parts, 2, 4096, p, p, p, p, p, p, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, None, None)
+        assert rc == -1 and b"lade_rope_kv_append: exactly one" in lib.lade_last_error_string()
+    for r, parts in ((p, p), (None, None)):
+        for sel, src_rows in ((None, 0), (p, 4)):
+            rc = lib.lade_add_rmsnorm(p, r, parts, 2, 4096, sel, src_rows, p, p, 4, 1024, 1e-5, cabi.LADE_BF16, None)
+            assert rc == -1 and b"lade_add_rmsnorm: exactly one" in lib.lade_last_error_string()
+    for gu, parts in ((p, p), (None, None)):
+        rc = lib.lade_silu_mul(gu, parts, 2, 4096, p, 4, 512, 0, cabi.LADE_BF16, None)
+        assert rc == -1 and b"lade_silu_mul: exactly one" in lib.lade_last_error_string()
+    # the partials of the two glue calls are 16-bit only (LADE_E_DTYPE, after the argument checks), need n_parts >= 1, and a row selection
+    # needs the number of source rows
+    assert lib.lade_add_rmsnorm(p, None, p, 2, 4096, None, 0, p, p, 4, 1024, 1e-5, cabi.LADE_F32, None) == -2
+    assert lib.lade_silu_mul(None, p, 2, 4096, p, 4, 512, 0, cabi.LADE_F32, None) == -2
+    assert lib.lade_add_rmsnorm(p, None, p, 0, 4096, None, 0, p, p, 4, 1024, 1e-5, cabi.LADE_BF16, None) == -1
+    assert lib.lade_silu_mul(None, p, 0, 4096, p, 4, 512, 0, cabi.LADE_BF16, None) == -1
+    assert lib.lade_add_rmsnorm(p, p, None, 0, 0, p, 0, p, p, 4, 1024, 1e-5, cabi.LADE_BF16, None) == -1
+    assert b"src_rows" in lib.lade_last_error_string()
+    assert lib.lade_add_rmsnorm(p, p, None, 0, 0, None, 0, p, p, 0, 1024, 1e-5, cabi.LADE_BF16, None) == 0      # no rows: nothing to launch
 
 
 def test_a_failure_inside_a_gemm_launch_keeps_its_own_code_and_message(lib):

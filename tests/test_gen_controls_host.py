@@ -133,10 +133,10 @@ def test_new_entry_points_validate_arguments(lib):
                 cand_rows=0, phase=2, pfp=0, tail=None)
     head = tuple(args.values())
     rest = (None, None, fake, None, None)
-    assert lib.lade_greedy_post_step_ex(*head, eos, 9, *rest) == -1
-    assert b"lade_greedy_post_step_ex" in lib.lade_last_error_string() and b"n_eos" in lib.lade_last_error_string()
-    assert lib.lade_greedy_post_step_ex(*head, None, 2, *rest) == -1
-    assert lib.lade_greedy_post_step_ex(*head, neg, 2, *rest) == -1
+    assert lib.lade_greedy_post_step(*head, eos, 9, *rest) == -1
+    assert b"lade_greedy_post_step:" in lib.lade_last_error_string() and b"n_eos" in lib.lade_last_error_string()
+    assert lib.lade_greedy_post_step(*head, None, 2, *rest) == -1
+    assert lib.lade_greedy_post_step(*head, neg, 2, *rest) == -1
     bad_head = head[:6] + (0,) + head[7:]                                                                    # W = 0
-    assert lib.lade_greedy_post_step_ex(*bad_head, eos, 2, *rest) == -1
-    assert lib.lade_greedy_post_step(*bad_head, 3, *rest) == -1 and b"lade_greedy_post_step:" in lib.lade_last_error_string()
+    assert lib.lade_greedy_post_step(*bad_head, eos, 2, *rest) == -1
+    assert lib.lade_greedy_post_step(*bad_head, None, 0, *rest) == -1 and b"lade_greedy_post_step:" in lib.lade_last_error_string()

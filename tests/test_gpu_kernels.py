@@ -643,7 +643,7 @@ def test_warp_rows_ties_follow_the_stable_order_and_dtypes():
 
 
 def test_add_rmsnorm_rows_equals_gather_then_add_rmsnorm():
-    """The step's row-pruned tail in one launch (lade_add_rmsnorm_rows) against its unfused form: fold the split-K partials, gather the
+    """The step's row-pruned tail in one launch (lade_add_rmsnorm with a row selection) against its unfused form: fold the split-K partials, gather the
     selected rows of x and of the residual, add + RMSNorm - bit for bit, for a plain residual and for 1..5 partials, all dtypes."""
     from lookaheaddecoding_amd import cabi, ops
     torch.manual_seed(7)

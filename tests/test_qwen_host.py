@@ -146,24 +146,36 @@ def test_ex_entry_points_validate_arguments(lib):
     from lookaheaddecoding_amd import cabi
     epi = cabi.QkvEpilogue(None, None, None, 1e-6)
     # null pointers: LADE_E_ARG, no launch
-    rc = lib.lade_rope_kv_append_ex(None, None, None, None, None, None, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, C.byref(epi), None)
-    assert rc == -1 and b"lade_rope_kv_append_ex" in lib.lade_last_error_string()
-    rc = lib.lade_rope_kv_append_parts_ex(None, 2, 0, None, None, None, None, None, None, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, None, None)
-    assert rc == -1 and b"lade_rope_kv_append_parts_ex" in lib.lade_last_error_string()
-    # bad shapes / a misaligned epilogue pointer / a head norm the partials path cannot reduce: LADE_E_ARG before any launch
+    rc = lib.lade_rope_kv_append(None, None, 0, 0, None, None, None, None, None, None, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, C.byref(epi), None)
+    assert rc == -1 and b"lade_rope_kv_append" in lib.lade_last_error_string()
+    rc = lib.lade_rope_kv_append(None, None, 2, 0, None, None, None, None, None, None, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, None, None)
+    assert rc == -1 and b"lade_rope_kv_append" in lib.lade_last_error_string()
     fake = 1 << 20            # never dereferenced: every call below fails its checks on the host
-    rc = lib.lade_rope_kv_append_ex(fake, fake, fake, fake, fake, fake, 4, 62, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, C.byref(epi), None)
+    for qkv, parts in ((fake, None), (None, fake)):                   # a source, but none of the other pointers / no q_out for the partials
+        rc = lib.lade_rope_kv_append(qkv, parts, 2, 0, None, None, None, None, None, None, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, None, None)
+        assert rc == -1 and b"lade_rope_kv_append: null pointer" in lib.lade_last_error_string()
+    rc = lib.lade_rope_kv_append(None, fake, 0, 4096, fake, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, None, None)
+    assert rc == -1 and b"n_parts" in lib.lade_last_error_string()     # the partials need n_parts >= 1
+    # bad shapes / a misaligned epilogue pointer / a head norm the partials path cannot reduce: LADE_E_ARG before any launch
+    rc = lib.lade_rope_kv_append(fake, None, 0, 0, None, fake, fake, fake, fake, fake, 4, 62, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, C.byref(epi), None)
     assert rc == -1                                                   # P + T > S_max
     bad = cabi.QkvEpilogue(fake + 2, None, None, 1e-6)
-    rc = lib.lade_rope_kv_append_ex(fake, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, C.byref(bad), None)
+    rc = lib.lade_rope_kv_append(fake, None, 0, 0, None, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, C.byref(bad), None)
     assert rc == -1 and b"aligned" in lib.lade_last_error_string()
     neg = cabi.QkvEpilogue(None, fake, None, -1.0)
-    rc = lib.lade_rope_kv_append_ex(fake, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, C.byref(neg), None)
+    rc = lib.lade_rope_kv_append(fake, None, 0, 0, None, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_BF16, C.byref(neg), None)
     assert rc == -1 and b"eps" in lib.lade_last_error_string()
     nrm = cabi.QkvEpilogue(None, fake, fake, 1e-6)
-    rc = lib.lade_rope_kv_append_parts_ex(fake, 2, 4096, fake, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 96, 64, 64, cabi.LADE_BF16,
-                                          C.byref(nrm), None)
+    rc = lib.lade_rope_kv_append(None, fake, 2, 4096, fake, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 96, 64, 64, cabi.LADE_BF16,
+                                 C.byref(nrm), None)
     assert rc == -1 and b"power of two" in lib.lade_last_error_string()
-    rc = lib.lade_rope_kv_append_parts_ex(fake, 2, 4096, fake, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_F32,
-                                          C.byref(nrm), None)
+    rc = lib.lade_rope_kv_append(None, fake, 2, 4096, fake, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 64, 64, 64, cabi.LADE_F32,
+                                 C.byref(nrm), None)
     assert rc == -2                                                   # the partials path is 16-bit only
+    # ... and so are the per-path shape rules: d = 12 (d/2 no multiple of 8) passes the checks of the materialised path only
+    rc = lib.lade_rope_kv_append(None, fake, 2, 4096, fake, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 12, 64, 64, cabi.LADE_BF16, None, None)
+    assert rc == -1 and b"d=12" in lib.lade_last_error_string()
+    rc = lib.lade_rope_kv_append(fake, None, 0, 0, None, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 7, 64, 64, cabi.LADE_BF16, None, None)
+    assert rc == -1 and b"d=7" in lib.lade_last_error_string()         # the materialised path needs an even d
+    rc = lib.lade_rope_kv_append(fake, None, 0, 0, None, fake, fake, fake, fake, fake, 4, 0, None, 2, 1, 64, 64, 64, 7, None, None)
+    assert rc == -2                                                   # unknown dtype

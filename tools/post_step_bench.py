@@ -1,6 +1,6 @@
 """lade_greedy_post_step alone: microseconds per launch in a hipGraph of 64 launches, steady phase, cold regime (random window tokens
 over a 32000-token pool that holds a few n-grams) and hot regime (few keys, full slots).  Optionally against another build of the
-library (`--old path/to/liblade_hip.so` with the round-3 signature: no record_host argument).
+library (`--old path/to/liblade_hip.so` with the round-3 signature: one scalar EOS id, no record_host argument).
     python tools/post_step_bench.py [--old _ab_old/lookaheaddecoding_amd/liblade_hip.so]"""
 import ctypes as C
 import os
@@ -38,11 +38,11 @@ def bench(lib, has_host, vocab_used, label):
     T = (N - 1) * W
     st = torch.cuda.current_stream().cuda_stream
     args = [ctl.data_ptr(), window.data_ptr(), wcap, pool_tok.data_ptr(), pool_cnt.data_ptr(), V, W, N, G, am.data_ptr(), W, guess.data_ptr(), T, 0, 2, 0,
-            tail.data_ptr(), -1, None, None, record.data_ptr()]
+            tail.data_ptr()] + ([None, 0] if has_host else [-1]) + [None, None, record.data_ptr()]      # EOS: the set (none) / the old scalar
     fn = lib.lade_greedy_post_step
     fn.restype = C.c_int
     vp, i = C.c_void_p, C.c_int32
-    fn.argtypes = [vp, vp, i, vp, vp, i, i, i, i, vp, i, vp, i, i, i, i, vp, i, vp, vp, vp] + ([vp] if has_host else []) + [vp]
+    fn.argtypes = [vp, vp, i, vp, vp, i, i, i, i, vp, i, vp, i, i, i, i, vp] + ([vp, i] if has_host else [i]) + [vp, vp, vp] + ([vp] if has_host else []) + [vp]
 
     def launch():
         a = args + ([rec_host.data_ptr() if '--no-host' not in sys.argv else None] if has_host else [])

@@ -1,11 +1,11 @@
 """Qwen2 / Qwen3 on the step engine: what the qkv epilogue costs.
 
-    python tools/qwen_step_bench.py kernel            # the epilogue kernel against the plain entry point (run it under
+    python tools/qwen_step_bench.py kernel            # the epilogue kernel against the call without an epilogue (run it under
                                                       #   rocprofv3 --kernel-trace --stats -- python tools/qwen_step_bench.py kernel)
     python tools/qwen_step_bench.py step [--steps K]  # lookahead step time (W15 N5 G15, hipGraph) and plain decoding per token
 
 `kernel`: at the step shape of qwen2.5-7b (bias) and qwen3-8b (head norm, and bias + norm), T = 60 rows of split-K partials (--parts of
-them, 2 by default), lade_rope_kv_append_parts and lade_rope_kv_append_parts_ex launched alternately on the same
+them, 2 by default), lade_rope_kv_append without and with the epilogue launched alternately on the same
 inputs, one launch per layer's K/V cache (the caches of all layers together are larger than the Infinity Cache, as in the step).
 The two kernels carry distinct names (rope_kv_append_kernel<T, false> / <T, true>), so the trace's per-kernel statistics are the A/B.
 `step`: both presets at full depth in bf16 (random weights; prompt of 128 tokens), the host clock around K hipGraph steps after a
@@ -55,7 +55,7 @@ def kernel(reps: int, n_parts: int) -> None:
             for _ in range(20):                            # warm-up
                 for li in range(L):
                     ops.rope_kv_append_parts(parts, n_parts, q, pos, cos, sin, kcs[li], vts[li], T, P, H=H, Hkv=Hkv, d=d)
-                    ops.rope_kv_append_parts_ex(parts, n_parts, q, pos, cos, sin, kcs[li], vts[li], T, P, H=H, Hkv=Hkv, d=d, epi=epi)
+                    ops.rope_kv_append_parts(parts, n_parts, q, pos, cos, sin, kcs[li], vts[li], T, P, H=H, Hkv=Hkv, d=d, epi=epi)
             t_plain = t_epi = 0.0
             for r in range(reps):                          # alternated: plain layer sweep, epilogue layer sweep
                 ev[0].record()
@@ -63,7 +63,7 @@ def kernel(reps: int, n_parts: int) -> None:
                     ops.rope_kv_append_parts(parts, n_parts, q, pos, cos, sin, kcs[li], vts[li], T, P, H=H, Hkv=Hkv, d=d)
                 ev[1].record()
                 for li in range(L):
-                    ops.rope_kv_append_parts_ex(parts, n_parts, q, pos, cos, sin, kcs[li], vts[li], T, P, H=H, Hkv=Hkv, d=d, epi=epi)
+                    ops.rope_kv_append_parts(parts, n_parts, q, pos, cos, sin, kcs[li], vts[li], T, P, H=H, Hkv=Hkv, d=d, epi=epi)
                 ev[2].record()
                 torch.cuda.synchronize()
                 t_plain += ev[0].elapsed_time(ev[1])
