@@ -46,7 +46,7 @@
  *   lade_rmsnorm / lade_embed_rmsnorm / lade_add_rmsnorm / lade_silu_mul / lade_gather_rows   LlamaRMSNorm (+ residual add), SwiGLU,
  *                            embedding / logits-row gather around the GEMMs
  *                            lade/models/modeling_llama.py:222-227, :360-380, :1164 ("next" row)
- *   lade_gemm_skinny / lade_gemm_skinny_kt / lade_weight_to_ktile / lade_weight_from_ktile / lade_splitk_reduce   the nn.Linear projections of the step at M = T <= 128 rows
+ *   lade_gemm_skinny / lade_gemm_skinny_kt / lade_gemm_qkv_rope / lade_qkv_pair_row / lade_weight_to_ktile / lade_weight_from_ktile / lade_splitk_reduce   the nn.Linear projections of the step at M = T <= 128 rows
  *                            lade/models/modeling_llama.py:360-380 (MLP), :492-494, :558 (q/k/v/o)
  *                            lade_rope_kv_append, lade_add_rmsnorm and lade_silu_mul also take that GEMM's fp32 split-K partials as
  *                            their input (the reduction is fused into the consumer); lade_rope_kv_append carries the qkv epilogue of
@@ -74,7 +74,9 @@ extern "C" {
                                  *    (+ lade_emit_init, lade_emit_rows);
                                  * 5: one entry point per kernel family, the source and the optional stages chosen by nullable arguments: lade_rope_kv_append
                                  *    (was + _ex, _parts, _parts_ex), lade_greedy_post_step (takes the EOS set; _ex removed), lade_add_rmsnorm (was + _parts,
-                                 *    _rows), lade_silu_mul (was + _parts) */
+                                 *    _rows), lade_silu_mul (was + _parts);
+                                 *    + lade_gemm_qkv_rope, lade_qkv_pair_row, lade_qkv_rope_args (additions only: no argument list that existed changed, so the
+                                 *    number stays - a library without them fails to load by the missing symbol) */
 
 /* error codes */
 #define LADE_OK 0
@@ -541,6 +543,32 @@ int lade_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t ldw, voi
 int lade_gemm_skinny_kt(const void* A, int64_t lda, const void* Wkt, void* C, int64_t ldc, float* Cpart,
                         int32_t M, int32_t N, int32_t K, int32_t n_split, int32_t bn, int32_t mb, int32_t mt, int32_t nt,
                         int32_t ring, int32_t epilogue, int32_t dtype, void* stream);
+/* The qkv projection of a decode step finished in ONE launch: the split-K GEMM with two K slices (the grid, slices and ring of lade_gemm_skinny(_kt) with
+ * n_split = 2), whose two work-groups per (n-block, m-block) reduce their pair themselves - each leaves its fp32 tile in Cpart with write-through stores and draws
+ * a ticket; the second to arrive reads the other tile, forms (0 + split 0) + split 1, rounds once to the model dtype and does what lade_rope_kv_append does
+ * with that value: q rotated to q_out [M][H*d], rotated k to K cache rows P .. P+M-1, v to the V^T cache.  Bit-identical to the two launches it replaces; no
+ * epilogue (bias / head norm) and no fp32.  Nothing spins and no co-residency is assumed.  The kernel streams the weight rows of a q or k head in PAIR ORDER
+ * (lade_qkv_pair_row) so that a rotation pair meets in one lane; W itself is the plain fused [q | k | v] weight, row-major (ktile = 0) or K-tile-major.
+ * Cpart: hand-off space of cpart_elems floats, >= ceil(N/bn) * ceil(M/(32 mb)) * 2 * 32 mb * bn (its contents afterwards are private to the kernel).
+ * tickets: n_tickets >= ceil(N/bn) * ceil(M/(32 mb)) int32, ZERO before the first launch; every launch leaves them zero (graph replays need no memset).
+ * bn a multiple of 32, mb, mt, nt explicit (>= 1); built for bn = 96, nt = 1 and (mb, mt) = (1,1), (2,1), (3,3), (4,2): anything else is LADE_E_ARG.
+ * d % 32 == 0, N == (H + 2 Hkv) d, K >= 128. */
+typedef struct lade_qkv_rope_args {
+    void* q_out;
+    const int32_t* positions;     /* [M] */
+    const void* cos_tab;          /* [max_pos][d], model dtype */
+    const void* sin_tab;
+    void* k_cache;                /* [Hkv][S_max][d] */
+    void* vt_cache;               /* [Hkv][d][S_max] */
+    const int32_t* dyn_P;         /* nullable: P read from the device (hipGraph steps); a step that would pass S_max writes nothing */
+    int32_t P, H, Hkv, d, S_max, max_pos;
+} lade_qkv_rope_args;
+int lade_gemm_qkv_rope(const void* A, int64_t lda, const void* W, int64_t ldw, int32_t ktile, float* Cpart, int64_t cpart_elems, int32_t* tickets,
+                       int32_t n_tickets, int32_t M, int32_t N, int32_t K, int32_t bn, int32_t mb, int32_t mt, int32_t nt, int32_t ring,
+                       const lade_qkv_rope_args* rope, int32_t dtype, void* stream);
+/* weight row that lands in row n of the fused kernel's tile order: per 32-row block of a q / k head [rows 16 b .. 16 b + 15 | rows d/2 + 16 b .. d/2 + 16 b + 15],
+ * v rows in place; -1 for arguments out of range (d % 32 != 0, n outside the fused weight).  Host only, no GPU needed. */
+int lade_qkv_pair_row(int32_t n, int32_t H, int32_t Hkv, int32_t d);
 int lade_weight_to_ktile(const void* W, int64_t ldw, void* Wkt, int32_t N, int32_t K, int32_t dtype, void* stream);
 /* the inverse, into a caller-provided row-major scratch W[N][ldw]: what a library GEMM needs (prefill chunks wider than 256 rows) when a
  * model too large to be held twice keeps its projection weights K-tile-major only */

@@ -67,6 +67,13 @@ class QkvEpilogue(C.Structure):
     _fields_ = [("bias", C.c_void_p), ("q_norm", C.c_void_p), ("k_norm", C.c_void_p), ("eps", C.c_float)]
 
 
+class QkvRopeArgs(C.Structure):
+    """lade_qkv_rope_args: the RoPE + KV append side of lade_gemm_qkv_rope"""
+    _fields_ = [("q_out", C.c_void_p), ("positions", C.c_void_p), ("cos_tab", C.c_void_p), ("sin_tab", C.c_void_p), ("k_cache", C.c_void_p),
+                ("vt_cache", C.c_void_p), ("dyn_P", C.c_void_p), ("P", C.c_int32), ("H", C.c_int32), ("Hkv", C.c_int32), ("d", C.c_int32),
+                ("S_max", C.c_int32), ("max_pos", C.c_int32)]
+
+
 class WarpParams(C.Structure):
     """lade_warp_params: the seven warper settings of lade_warp_rows_ex, in HF's order of application"""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float), ("typical_p", C.c_float),
@@ -125,6 +132,8 @@ SIGNATURES = {
     "lade_gather_rows": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "lade_gemm_skinny": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "lade_gemm_skinny_kt": [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "lade_gemm_qkv_rope": [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(QkvRopeArgs), _i32, _vp],
+    "lade_qkv_pair_row": [_i32, _i32, _i32, _i32],
     "lade_weight_to_ktile": [_vp, _i64, _vp, _i32, _i32, _i32, _vp],
     "lade_weight_from_ktile": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "lade_splitk_reduce": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
@@ -170,7 +179,8 @@ def debug(name: str, default=None):
     """One experiment switch of `LADE_DEBUG=name[=value],name2[=value2],...` (read at every call: tests flip them at run time): the kernel
     ablation bits and tuner experiments that only tools/ and A/B runs use - gemm_dbg, attn_dbg, attn_shape, attn_splits, attn_split_rule,
     combine_hpb (those six are read by the library itself), tune_consumer, gu_tail_fixed, tune_ring, tune_verbose, attn_tune, row_classes,
-    draw_torch, fuse_tail, poll_reads_per_yield.  A bare name means "1"."""
+    draw_torch, fuse_tail, poll_reads_per_yield, qkv_rope (0: the qkv GEMM never carries RoPE + the KV append, 1: wherever it can - the two
+    arms of the launch's A/B; unset: the row class's decision).  A bare name means "1"."""
     s = os.environ.get("LADE_DEBUG")
     if not s:
         return default

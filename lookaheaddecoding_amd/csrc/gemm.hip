@@ -118,6 +118,54 @@ extern "C" int lade_gemm_skinny_kt(const void* A, int64_t lda, const void* Wkt, 
     return gemm_skinny(A, lda, Wkt, 8, true, C, ldc, Cpart, M, N, K, n_split, bn, mb, mt, nt, ring, epilogue, dtype, stream);
 }
 
+// The qkv projection with two K splits, finished in its own launch: the two work-groups of an (n-block, m-block) hand their fp32 tiles to each
+// other through Cpart and the second to arrive sums, rounds, rotates q and k and appends K / V^T (gemm_kernel.hpp: gemm_rope_epilogue) - what
+// lade_gemm_skinny(_kt) with n_split = 2 followed by lade_rope_kv_append on the partials computes, bit for bit.  Explicit launch shape only
+// (mb, mt, nt >= 1, bn a multiple of 32); a shape the fused kernel is not built for is LADE_E_ARG, and the caller keeps the two launches.
+extern "C" int lade_gemm_qkv_rope(const void* A, int64_t lda, const void* W, int64_t ldw, int32_t ktile, float* Cpart, int64_t cpart_elems,
+                                  int32_t* tickets, int32_t n_tickets, int32_t M, int32_t N, int32_t K, int32_t bn, int32_t mb, int32_t mt, int32_t nt,
+                                  int32_t ring, const lade_qkv_rope_args* rope, int32_t dtype, void* stream) {
+    LADE_REQUIRE(ring == 0 || (ring >= 2 && ring <= 6) || ring == 8, LADE_E_ARG, "lade_gemm_qkv_rope: ring=%d", ring);
+    LADE_REQUIRE(A && W && Cpart && tickets && rope && M > 0 && N > 0 && K > 0, LADE_E_ARG, "lade_gemm_qkv_rope: null pointer or M=%d N=%d K=%d", M, N, K);
+    LADE_REQUIRE(K % G_BK == 0 && K / G_BK >= 2 && lda % 8 == 0 && ldw % 8 == 0, LADE_E_ARG,
+                 "lade_gemm_qkv_rope: K=%d must be a multiple of %d with a K tile per split, strides multiples of 8", K, G_BK);
+    LADE_REQUIRE(dtype == LADE_BF16 || dtype == LADE_F16, LADE_E_DTYPE, "lade_gemm_qkv_rope: dtype=%d", dtype);
+    LADE_REQUIRE(bn >= 32 && bn <= 256 && bn % 32 == 0 && mb >= 1 && mb <= 4 && mt >= 1 && mb % mt == 0 && nt >= 1 && (bn / 32) % nt == 0, LADE_E_ARG,
+                 "lade_gemm_qkv_rope: bn=%d mb=%d mt=%d nt=%d", bn, mb, mt, nt);
+    const lade_qkv_rope_args& a = *rope;
+    LADE_REQUIRE(a.q_out && a.positions && a.cos_tab && a.sin_tab && a.k_cache && a.vt_cache, LADE_E_ARG, "lade_gemm_qkv_rope: null pointer in the RoPE arguments");
+    // a rotation pair must sit in one 32-row MFMA block: heads of whole blocks
+    LADE_REQUIRE(a.H > 0 && a.Hkv > 0 && a.d > 0 && a.d % 32 == 0 && a.d <= 256 && (int64_t)(a.H + 2 * a.Hkv) * a.d == N, LADE_E_ARG,
+                 "lade_gemm_qkv_rope: H=%d Hkv=%d d=%d do not make N=%d rows of whole 32-row blocks", a.H, a.Hkv, a.d, N);
+    LADE_REQUIRE(a.P >= 0 && a.S_max > 0 && a.max_pos > 0 && (int64_t)a.P + M <= a.S_max, LADE_E_ARG, "lade_gemm_qkv_rope: T=%d P=%d S_max=%d max_pos=%d", M, a.P,
+                 a.S_max, a.max_pos);
+    const int bm = 32 * mb;
+    const int64_t n_tiles = (int64_t)cdiv(N, bn) * cdiv(M, bm);
+    LADE_REQUIRE(n_tiles <= n_tickets && n_tiles * 2 * bm * bn <= cpart_elems, LADE_E_ARG,
+                 "lade_gemm_qkv_rope: %lld tiles of %d x %d need %lld fp32 of hand-off space and as many tickets as tiles (got %lld, %d)", (long long)n_tiles, bm, bn,
+                 (long long)(n_tiles * 2 * bm * bn), (long long)cpart_elems, n_tickets);
+    GemmK g;
+    g.A = (const uint16_t*)A; g.W = (const uint16_t*)W; g.C = nullptr; g.Cpart = Cpart;
+    g.lda = lda; g.ldw = ktile ? 8 : ldw; g.ldc = 0; g.M = M; g.N = N; g.K = K; g.n_split = 2;
+    g.w_ts = ktile ? (int64_t)N * G_BK : 0;
+    g.dbg = 0;
+    g.epi = 0;
+    g.n_stage = ring;
+    RopeK r;
+    r.positions = a.positions; r.cos_tab = (const uint16_t*)a.cos_tab; r.sin_tab = (const uint16_t*)a.sin_tab; r.q_out = (uint16_t*)a.q_out;
+    r.k_cache = (uint16_t*)a.k_cache; r.vt_cache = (uint16_t*)a.vt_cache; r.dyn_P = a.dyn_P; r.tickets = tickets;
+    r.P = a.P; r.H = a.H; r.Hkv = a.Hkv; r.d = a.d; r.S_max = a.S_max; r.max_pos = a.max_pos;
+    const int rc = gemm_rope_dispatch(dtype, g, r, (hipStream_t)stream, mb / mt, mt, bn / 32 / nt, nt);
+    if (rc != GEMM_NOT_IN_TABLE) return rc;
+    LADE_REQUIRE(false, LADE_E_ARG, "lade_gemm_qkv_rope: no fused kernel for mb=%d mt=%d bn=%d nt=%d", mb, mt, bn, nt);
+}
+
+// tile-order row -> weight row of the fused qkv kernel (gemm_decl.hpp: qkv_pair_row), for callers and tests that want the order itself; -1 = bad arguments
+extern "C" int lade_qkv_pair_row(int32_t n, int32_t H, int32_t Hkv, int32_t d) {
+    if (H <= 0 || Hkv <= 0 || d <= 0 || d % 32 != 0 || n < 0 || n >= (H + 2 * Hkv) * d) return -1;
+    return qkv_pair_row(n, H, Hkv, d);
+}
+
 // Wkt[kt][n][0..63] = W[n][64 kt .. 64 kt + 63]: one 16-byte chunk per thread, a wave writes 1 KiB contiguous
 extern "C" int lade_weight_to_ktile(const void* W, int64_t ldw, void* Wkt, int32_t N, int32_t K, int32_t dtype, void* stream) {
     LADE_REQUIRE(W && Wkt && W != Wkt && N > 0 && K > 0 && K % G_BK == 0 && ldw >= K && ldw % 8 == 0, LADE_E_ARG,

@@ -241,14 +241,136 @@ __device__ __forceinline__ void gemm_epilogue(const GemmK& g, f32x16 (&acc)[MT][
     }
 }
 
+// Tail of the fused qkv kernel (n_split == 2): what lade_rope_kv_append does on the two partials, inside the GEMM's launch.  Both work-groups of
+// an (n-block, m-block) leave their fp32 tile in their half of the pair's hand-off slot with write-through stores - straight from the
+// accumulators, 16 bytes per lane, a wave's stores contiguous - wait for them, and draw a ticket.  The first leaves.  The second acquires, reads
+// the partner's tile back in the same order and forms (0 + p_split0) + p_split1 whichever split it is, rounds once to the model dtype - the value
+// load_parts (glue.hip) hands the RoPE kernel - and then runs that kernel's arithmetic on it: a lane holds activation row ql and, per 32-row
+// block in pair order, accumulators e (i = 16 b + 8 g4 + 4 hi + e, g4 < 2) and e + 8 (i + d/2).  Nothing waits for anybody: no spin, no
+// co-residency assumed.  The second arriver puts the counter back to zero, so a replayed graph finds it as the first launch did.
+template <typename T, int MW, int MT, int NG, int NT>
+__device__ __forceinline__ void gemm_rope_epilogue(const GemmK& g, const RopeK& r, f32x16 (&acc)[MT][NT], unsigned char* smem, int mw, int ng, bool computes, int n0,
+                                                   int m0, int split) {
+    constexpr int BN = 32 * NT * NG, BM = 32 * MW * MT, CT = MW * NG * 64;      // CT: threads that hold accumulators
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int ql = lane & 31, hi = lane >> 5;
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    g_barrier();                                             // the ring is free: its first word carries the ticket below
+    const size_t tile = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
+    float* slot = g.Cpart + tile * 2 * (size_t)(BM * BN);
+    float* mine = slot + (size_t)split * (BM * BN);
+    const float* other = slot + (size_t)(split ^ 1) * (BM * BN);
+    if (computes)
+#pragma unroll
+        for (int a = 0; a < MT; ++a)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const u32x4 vv = u32x4{__float_as_uint(acc[a][j][4 * g4 + 0]), __float_as_uint(acc[a][j][4 * g4 + 1]), __float_as_uint(acc[a][j][4 * g4 + 2]),
+                                           __float_as_uint(acc[a][j][4 * g4 + 3])};
+                    float* dstp = mine + ((size_t)((a * NT + j) * 4 + g4) * CT + tid) * 4;
+                    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dstp), "v"(vv) : "memory");
+                }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // every storing wave: its write-through stores have landed
+    g_barrier();
+    int* flag = reinterpret_cast<int*>(smem);
+    if (tid == 0) {
+        const int t = __hip_atomic_fetch_add(r.tickets + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t != 0) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(r.tickets + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        *flag = t;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    g_barrier();
+    if (*flag == 0 || !computes) return;
+    int P = r.P;
+    if (r.dyn_P) {
+        P = *r.dyn_P;
+        if (P + g.M > r.S_max) return;      // device-side cache length (hipGraph steps): never write K/V rows past the cache
+    }
+    const int d = r.d, half = d >> 1;
+#pragma unroll
+    for (int a = 0; a < MT; ++a) {
+        const int m = m0 + (mw * MT + a) * 32 + ql;
+        const bool row_ok = m < g.M;          // a padded row of the last m-block writes nothing
+        int pos = row_ok ? r.positions[m] : 0;
+        pos = pos < 0 ? 0 : (pos >= r.max_pos ? r.max_pos - 1 : pos);
+        const uint16_t* c = r.cos_tab + (size_t)pos * d;
+        const uint16_t* s = r.sin_tab + (size_t)pos * d;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int nrow = n0 + (ng * NT + j) * 32;          // first row (tile order) of this 32-row block: inside one head
+            if (nrow >= g.N) continue;
+            float4 ov[4];
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) ov[g4] = *reinterpret_cast<const float4*>(other + ((size_t)((a * NT + j) * 4 + g4) * CT + tid) * 4);
+            float v[16];
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const float o4[4] = {ov[g4].x, ov[g4].y, ov[g4].z, ov[g4].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float own = acc[a][j][4 * g4 + e];
+                    const float p0 = split == 0 ? own : o4[e], p1 = split == 0 ? o4[e] : own;
+                    v[4 * g4 + e] = to_f32<T>(from_f32<T>(__fadd_rn(__fadd_rn(0.f, p0), p1)));
+                }
+            }
+            const int h = nrow / d, rb = nrow - h * d;
+            if (h < r.H + r.Hkv) {
+                // (one base pointer and two offsets: a select between two pointer expressions came out of the f16 build as a table in scratch memory)
+                const size_t dq = ((size_t)m * r.H + h) * d, dk = ((size_t)(h - r.H) * r.S_max + P + m) * d;
+                uint16_t* dst = r.q_out + (h < r.H ? dq : (size_t)(r.k_cache - r.q_out) + dk);
+#pragma unroll
+                for (int g4 = 0; g4 < 2; ++g4) {
+                    const int i = (rb >> 1) + 8 * g4 + 4 * hi;          // 16 b + ..: rb = 32 b
+                    if (row_ok) {
+                        const u32x2 c1 = *reinterpret_cast<const u32x2*>(c + i), c2 = *reinterpret_cast<const u32x2*>(c + i + half);
+                        const u32x2 s1 = *reinterpret_cast<const u32x2*>(s + i), s2 = *reinterpret_cast<const u32x2*>(s + i + half);
+                        float o1[4], o2[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float a1 = v[4 * g4 + e], a2 = v[4 * (g4 + 2) + e];
+                            const float fc1 = to_f32<T>((uint16_t)(c1[e >> 1] >> (16 * (e & 1)))), fc2 = to_f32<T>((uint16_t)(c2[e >> 1] >> (16 * (e & 1))));
+                            const float fs1 = to_f32<T>((uint16_t)(s1[e >> 1] >> (16 * (e & 1)))), fs2 = to_f32<T>((uint16_t)(s2[e >> 1] >> (16 * (e & 1))));
+                            // q*cos + rotate_half(q)*sin, rotate_half = cat(-x2, x1); one rounding per torch op (kv.hip: rope_kv_append_kernel)
+                            o1[e] = __fadd_rn(rnd<T>(__fmul_rn(a1, fc1)), rnd<T>(__fmul_rn(-a2, fs1)));
+                            o2[e] = __fadd_rn(rnd<T>(__fmul_rn(a2, fc2)), rnd<T>(__fmul_rn(a1, fs2)));
+                        }
+                        u32x2 w1, w2;
+                        w1[0] = (uint32_t)from_f32<T>(o1[0]) | ((uint32_t)from_f32<T>(o1[1]) << 16);
+                        w1[1] = (uint32_t)from_f32<T>(o1[2]) | ((uint32_t)from_f32<T>(o1[3]) << 16);
+                        w2[0] = (uint32_t)from_f32<T>(o2[0]) | ((uint32_t)from_f32<T>(o2[1]) << 16);
+                        w2[1] = (uint32_t)from_f32<T>(o2[2]) | ((uint32_t)from_f32<T>(o2[3]) << 16);
+                        *reinterpret_cast<u32x2*>(dst + i) = w1;
+                        *reinterpret_cast<u32x2*>(dst + i + half) = w2;
+                    }
+                }
+            } else if (row_ok) {
+                // V^T[kv head][dd][P + m]: the 32 lanes of a half wave are 32 consecutive tokens of one dd
+                uint16_t* vt = r.vt_cache + ((size_t)(h - r.H - r.Hkv) * d + rb + 4 * hi) * r.S_max + P + m;
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) vt[(size_t)(8 * g4 + e) * r.S_max] = from_f32<T>(v[4 * g4 + e]);
+            }
+        }
+    }
+}
+
 // Work-group tile = BM activation rows x BN weight rows, BM = 32*MW*MT, BN = 32*NG*NT: the waves form an MW x NG grid
 // (MW*NG <= 8 waves compute, all 8 issue DMA; m-group = w % MW, n-group = w / MW) and one wave owns MT x NT MFMA tiles
 // of 32 x 32.  Per 16-deep K step a wave reads MT activation + NT weight fragments from LDS for MT*NT MFMAs, so the LDS
 // bytes read per weight byte are 8 waves * (MT + NT) / (NG*NT) ... = (MT + NT) / NT * MW (+ the DMA write): with MT = 1 a
 // 128-row step moves ~7 LDS bytes per weight byte and the 128 B/clk LDS port caps a CU at ~38 GB/s of weights; 2 x 2
 // wave tiles bring that to ~5.5.
-template <typename T, int MW, int MT, int NG, int NT>
-__global__ __launch_bounds__(G_THREADS) void gemm_skinny_kernel(GemmK g) {
+// The body of both kernels.  ROPE = the qkv GEMM with the fused tail: the weight rows arrive in pair order (qkv_pair_row) and the epilogue is
+// gemm_rope_epilogue; rp is null otherwise.
+template <typename T, int MW, int MT, int NG, int NT, bool ROPE>
+__device__ __forceinline__ void gemm_skinny_body(const GemmK& g, const RopeK* rp) {
     static_assert(MW * NG <= 8, "at most 8 computing waves");
     constexpr int NW = G_THREADS / 64;          // all 8 waves move DMA pieces, the first MW * NG of them compute
     constexpr int MB = MW * MT;
@@ -292,7 +414,9 @@ __global__ __launch_bounds__(G_THREADS) void gemm_skinny_kernel(GemmK g) {
         const int p = isw ? piece : piece - W_PIECES;
         const int row = p * 8 + (lane >> 3);
         const int c = (lane & 7) ^ ((row >> 1) & 7);
-        p_src[i] = (isw ? g.W + (size_t)min(n0 + row, g.N - 1) * w_rs + (size_t)t0 * w_ts
+        int wrow = min(n0 + row, g.N - 1);
+        if constexpr (ROPE) wrow = qkv_pair_row(wrow, rp->H, rp->Hkv, rp->d);
+        p_src[i] = (isw ? g.W + (size_t)wrow * w_rs + (size_t)t0 * w_ts
                         : g.A + (size_t)min(m0 + row, g.M - 1) * g.lda + (size_t)t0 * G_BK) + c * 8;
         if (!isw && (g.dbg & 128)) p_src[i] = g.A + (lane & 7) * 8;        // ablation (tools/gemm_ingest_probe.py): every activation piece re-reads one cached 128-byte line
         p_dst[i] = (isw ? 0 : W_BYTES) + p * 1024;
@@ -373,7 +497,18 @@ __global__ __launch_bounds__(G_THREADS) void gemm_skinny_kernel(GemmK g) {
         default: main_loop(std::integral_constant<int, 4>{}); break;
     }
 
-    gemm_epilogue<T, MW, MT, NG, NT>(g, acc, smem, mw, ng, computes, n0, m0, split);
+    if constexpr (ROPE) gemm_rope_epilogue<T, MW, MT, NG, NT>(g, *rp, acc, smem, mw, ng, computes, n0, m0, split);
+    else gemm_epilogue<T, MW, MT, NG, NT>(g, acc, smem, mw, ng, computes, n0, m0, split);
+}
+
+template <typename T, int MW, int MT, int NG, int NT>
+__global__ __launch_bounds__(G_THREADS) void gemm_skinny_kernel(GemmK g) {
+    gemm_skinny_body<T, MW, MT, NG, NT, false>(g, nullptr);
+}
+
+template <typename T, int MW, int MT, int NG, int NT>
+__global__ __launch_bounds__(G_THREADS) void gemm_qkv_rope_kernel(GemmK g, RopeK r) {
+    gemm_skinny_body<T, MW, MT, NG, NT, true>(g, &r);
 }
 
 // sums the n_split fp32 partials in split order and writes the model dtype:  C[m][n] = sum_s part[s][m][n]
@@ -399,6 +534,25 @@ static int launch_gemm(const GemmK& g0, hipStream_t st) {
     dim3 grid(cdiv(g.N, BN), g.n_split, cdiv(g.M, BM));
     hipLaunchKernelGGL((gemm_skinny_kernel<T, MW, MT, NG, NT>), grid, dim3(G_THREADS), lds, st, g);
     return check_launch("lade_gemm_skinny");
+}
+
+// the fused qkv launch: the same grid, K slices and ring as launch_gemm gives the two-split GEMM it replaces
+template <typename T, int MW, int MT, int NG, int NT>
+static int launch_gemm_rope(const GemmK& g0, const RopeK& r, hipStream_t st) {
+    constexpr int BN = 32 * NT * NG, BM = 32 * MW * MT;
+    constexpr size_t STAGE = (size_t)(BN + BM) * 128;
+    GemmK g = g0;
+    if (g.n_stage == 0) g.n_stage = g_stages(BN, BM);
+    LADE_REQUIRE(g.n_stage >= 2 && g.n_stage <= G_NSTAGE_CAP && g.n_stage != 7 && g.n_stage * STAGE <= (size_t)G_LDS_MAX, LADE_E_ARG,
+                 "lade_gemm_qkv_rope: a ring of %d stages of %d + %d rows does not fit the %d KB of LDS", g.n_stage, BN, BM, G_LDS_MAX / 1024);
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)gemm_qkv_rope_kernel<T, MW, MT, NG, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS_MAX);
+        attr = true;
+    }
+    dim3 grid(cdiv(g.N, BN), 2, cdiv(g.M, BM));
+    hipLaunchKernelGGL((gemm_qkv_rope_kernel<T, MW, MT, NG, NT>), grid, dim3(G_THREADS), g.n_stage * STAGE, st, g, r);
+    return check_launch("lade_gemm_qkv_rope");
 }
 
 // the shapes that are built: (wave grid MW x NG, MT x NT MFMA tiles per wave)

@@ -173,6 +173,7 @@ class StepEngine(KernelDecisions):
         # decides: the 128-row shape, the sqrt split rule.  The leading 0 is where the tables kept "RoPE + KV append inside the launch": those forms
         # measured slower and were removed; the slot stays so that old and new tune files read alike
         self.attn_cfg = {}
+        self.qkv_rope = {}                  # row class -> the qkv GEMM carries RoPE + the KV append in its epilogue (tuning.use_qkv_rope)
         if cabi.debug("fuse_rope", "0") in ("1", "2"):
             raise cabi.LadeHipError("LADE_DEBUG=fuse_rope: the fused RoPE + KV append attention forms were removed (measured slower: DESIGN 4.9)")
         # work-group rows of the attention launch: 128, but 64 where eight or more heads share a KV head (Llama-2-70B: 480 rows per KV head at T = 60) -
@@ -199,7 +200,8 @@ class StepEngine(KernelDecisions):
         if self.custom_gemm and env_tf not in ("off", "none", "0"):
             if self.tune_file:
                 self._load_tune_file(self.tune_file, strict=True)
-            if not self.tune_loaded:
+            # (LADE_TUNE_SHIPPED=0: measure instead of adopting the shipped table - tools/make_tune_table.py, which writes that table)
+            if not self.tune_loaded and os.environ.get("LADE_TUNE_SHIPPED", "1") != "0":
                 shipped = shipped_tune_table(self.device)
                 if os.path.exists(shipped):
                     self._load_tune_file(shipped, strict=False)
@@ -384,6 +386,8 @@ class StepEngine(KernelDecisions):
         if self.custom_gemm:
             self.ws_part = torch.empty(16 * 128 * max(qkv_w, 2 * self.inter, self.hidden), dtype=torch.float32, device=dev)
             self.ws_q = torch.empty(max_T, self.H * self.d, dtype=dt, device=dev)
+            # ticket counters of the fused qkv launch's pair hand-off, one per (n-block, m-block): zero here, and every launch leaves them zero
+            self.ws_tickets = torch.zeros(-(-qkv_w // 32) * -(-max_T // 32), dtype=torch.int32, device=dev)
 
     def grow(self, max_seq: int, max_T: int, keep_rows: int = 0) -> None:
         """Enlarges the KV cache and / or the step workspaces in place (the fused weights stay): the first keep_rows cache
@@ -468,6 +472,7 @@ class StepEngine(KernelDecisions):
             ops.gather_rows(self.embed, ids, out=x, rows=T)
         rpos, rcos, rsin = (pos, self.cos, self.sin) if self._ntk is None else self._ntk_rows(pos, T, P, dyn_P, rope_len, ntk_pad)
         part = self.ws_part if fused else None
+        qkv_rope = self.use_qkv_rope(mclass, cfg_qkv)          # the qkv GEMM finishes RoPE + the KV append itself: no launch of their own
         r_parts = 0                     # > 0: the pending residual branch lives in `part` as that many split-K partials
         for li, lw in enumerate(self.layers):
             if li == 0 and fuse_embed:
@@ -478,7 +483,11 @@ class StepEngine(KernelDecisions):
                 ops.add_rmsnorm_parts(x, part, r_parts, lw["ln1"], self.eps, out=h)   # x += mlp(prev); h = norm(x)
             else:
                 ops.add_rmsnorm(x, r, lw["ln1"], self.eps, out=h)
-            if cfg_qkv:
+            if qkv_rope:
+                qb = self.ws_q[:T]
+                cfg_qkv.gemm_qkv_rope(h, self._w(lw, "wqkv"), part, self.ws_tickets, qb, rpos, rcos, rsin, self.k_cache(li), self.vt_cache(li), P, H, Hkv, d, dyn_P)
+                q_in = qb
+            elif cfg_qkv:
                 cfg_qkv.gemm_parts(h, self._w(lw, "wqkv"), part)
                 qb = self.ws_q[:T]
                 if self.skip_attn != "all":

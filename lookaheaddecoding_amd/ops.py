@@ -449,6 +449,38 @@ def gemm_parts(a: torch.Tensor, w: torch.Tensor, part: torch.Tensor, n_split: in
     _gemm(a, w, None, 0, ptr(part), n_split, bn, mb, mt, nt, 0, ring)
 
 
+QKV_ROPE_SHAPES = {(1, 1), (2, 1), (3, 3), (4, 2)}       # (mb, mt) the fused qkv kernel is built for, at bn = 96, nt = 1 (csrc/gemm_qkv_rope.hip)
+
+
+def gemm_qkv_rope(a: torch.Tensor, w: torch.Tensor, part: torch.Tensor, tickets: torch.Tensor, q_out: torch.Tensor, positions: torch.Tensor,
+                  cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor, vt_cache: torch.Tensor, P: int, *, H: int, Hkv: int, d: int,
+                  bn: int, mb: int, mt: int, nt: int, ring: int = 0, dyn_P: Optional[torch.Tensor] = None) -> None:
+    """gemm_parts with two splits + rope_kv_append_parts in ONE launch (`lade_gemm_qkv_rope`): the two work-groups of an n-block reduce their
+    pair themselves and the second to arrive rotates q / k and appends K / V^T.  Same bits in q_out and the cache rows as the two launches.
+    part: the hand-off space (fp32; its contents afterwards mean nothing to a caller); tickets: int32, zero before the first launch, left zero."""
+    M, N = a.shape[0], weight_rows(w)
+    assert a.stride(1) == 1 and part.dtype == torch.float32 and tickets.dtype == torch.int32 and positions.dtype == torch.int32 and positions.numel() >= M
+    assert cos.dtype == a.dtype and cos.shape[1] == d and cos.is_contiguous() and sin.is_contiguous() and q_out.is_contiguous() and q_out.dtype == a.dtype
+    assert q_out.numel() >= M * H * d and k_cache.dtype == a.dtype and vt_cache.dtype == a.dtype
+    kt = w.dim() == 3
+    if kt:
+        assert w.is_contiguous() and w.shape[0] * 64 == a.shape[1] and w.shape[2] == 64
+    else:
+        assert w.shape[1] == a.shape[1] and w.stride(1) == 1
+    rope = cabi.QkvRopeArgs(ptr(q_out), ptr(positions), ptr(cos), ptr(sin), ptr(k_cache), ptr(vt_cache), ptr(dyn_P), P, H, Hkv, d, k_cache.shape[1],
+                            cos.shape[0])
+    call("lade_gemm_qkv_rope", ptr(a), a.stride(0), ptr(w), 8 if kt else w.stride(0), int(kt), ptr(part), part.numel(), ptr(tickets), tickets.numel(), M, N,
+         a.shape[1], bn, mb, mt, nt, ring, C.byref(rope), dtype_code(a))
+
+
+def qkv_pair_row(n: int, H: int, Hkv: int, d: int) -> int:
+    """the weight row the fused qkv kernel streams into row n of its tile order (`lade_qkv_pair_row`; host only)"""
+    r = cabi.lib().lade_qkv_pair_row(n, H, Hkv, d)
+    if r < 0:
+        raise cabi.LadeHipError(f"lade_qkv_pair_row: n={n} H={H} Hkv={Hkv} d={d}")
+    return r
+
+
 def add_rmsnorm_parts(x: torch.Tensor, part: torch.Tensor, n_parts: int, w: torch.Tensor, eps: float, out: torch.Tensor) -> torch.Tensor:
     """add_rmsnorm with the residual as the first n_parts fp32 split-K partials of `part` ([n_parts][rows][hidden])"""
     rows, hidden = x.shape

@@ -59,7 +59,17 @@ class GemmCfg(NamedTuple):
         """of a gate/up decision: the unsplit variant that carries SwiGLU in its epilogue (no partials, no SwiGLU launch)"""
         return self.n_split == 1
 
+    @property
+    def rope_fusable(self) -> bool:
+        """of a qkv decision: two splits in a shape the fused kernel is built for - the launch can carry RoPE + the KV append in its epilogue (no
+        RoPE launch, no flushed partials).  Whether it does is the row class's `qkv_rope` flag (KernelDecisions.use_qkv_rope)."""
+        return self.n_split == 2 and self.bn == 96 and self.nt == 1 and (self.mb, self.mt) in ops.QKV_ROPE_SHAPES
+
     # the one place each launch kind's argument order is written
+    def gemm_qkv_rope(self, a, w, part, tickets, q_out, positions, cos, sin, k_cache, vt_cache, P, H, Hkv, d, dyn_P) -> None:
+        ops.gemm_qkv_rope(a, w, part, tickets, q_out, positions, cos, sin, k_cache, vt_cache, P, H=H, Hkv=Hkv, d=d, bn=self.bn, mb=self.mb, mt=self.mt,
+                          nt=self.nt, ring=self.ring, dyn_P=dyn_P)
+
     def gemm_parts(self, a, w, part) -> None:
         ops.gemm_parts(a, w, part, self.n_split, self.bn, self.mb, self.mt, self.nt, self.ring)
 
@@ -228,6 +238,20 @@ class KernelDecisions:
         """the row class a T-row step runs in (None above the last one: the library GEMMs)"""
         return next((m for m in self.ROW_CLASSES if T <= m), None)
 
+    def use_qkv_rope(self, mclass: Optional[int], cfg_qkv) -> bool:
+        """whether the qkv GEMM of this row class finishes RoPE + the KV append in its own launch (lade_gemm_qkv_rope) instead of handing two
+        partials to lade_rope_kv_append.  Only where the fused kernel computes the same bits: a two-split decision in a built shape, 16-bit, heads
+        of whole 32-row blocks, no qkv epilogue (Qwen bias / head norm) and no dynamic-NTK rows.  Then the row class's flag decides - taken by
+        the in-step pass or read from the tune file (`wqkv_rope`) - unless LADE_DEBUG=qkv_rope=0 (never: the A/B arm of the two-launch path) or
+        =1 (wherever it is possible) overrides it."""
+        if (mclass is None or cfg_qkv is None or not cfg_qkv.rope_fusable or self.dtype == torch.float32 or self.d % 32 != 0 or self.has_epilogue
+                or self._ntk is not None or self.skip_attn == "all"):
+            return False
+        forced = cabi.debug("qkv_rope")
+        if forced is not None:
+            return str(forced) != "0"
+        return bool(self.qkv_rope.get(mclass, False))
+
     def _decide(self, mclass: int, *, allow_grow: bool = False, skip_in_capture: bool = False) -> None:
         """The one gate of forward(), attn_choice(), prepare() and tune_all(): takes the decisions of a row class that is still open - the
         isolated pass of the four layer projections, then the in-step pass.  The isolated pass must be over before a step writes its first
@@ -301,6 +325,8 @@ class KernelDecisions:
                 if n in row:
                     v = row[n]
                     self.gemm_cfg[(n, m)] = None if v is None else GemmCfg(*(int(x) for x in v))
+            if row.get("wqkv_rope"):            # the qkv launch of this class carries RoPE + the KV append (use_qkv_rope)
+                self.__dict__.setdefault("qkv_rope", {})[m] = True
             if "attn" in row:
                 if int(row["attn"][0]) != 0:        # the slot of the fused RoPE + KV append forms (removed: DESIGN 4.9)
                     raise cabi.LadeHipError(f"LADE_TUNE_FILE={path}: row class {m} selects a fused-RoPE attention form ({row['attn'][:3]}), which this library no longer has")
@@ -335,6 +361,11 @@ class KernelDecisions:
                     c = self.gemm_cfg[(n, m)]
                     row[n] = None if c is None else list(c)
                 row["attn"] = list(self.attn_cfg.get(m, self.attn_default))
+                flags = getattr(self, "qkv_rope", None)
+                if flags is not None and flags.get(m):              # (written only where set: tables without the fused launch stay as they were)
+                    row["wqkv_rope"] = 1
+                elif flags is not None:
+                    row.pop("wqkv_rope", None)
             if ("lm_head", m) in self.gemm_cfg:
                 c = self.gemm_cfg[("lm_head", m)]
                 row["lm_head"] = None if c is None else list(c)
@@ -472,7 +503,7 @@ class KernelDecisions:
         ctx = min(self.STEP_TUNE_CONTEXT, self.S_max)
         skey = (self.hidden, self.inter, self.H, self.Hkv, self.d, self.L, mclass, str(self.dtype), torch.cuda.get_device_name(self.device),
                 self.n_cu, tuple(self.kt_names), self.gu_layout, tuple(self.gemm_cfg[(n, mclass)] for n in self.LAYER_GEMMS), ctx, self.attn_default,
-                cabi.debug("attn_tune", "0"), self.qkv_bias, self.qk_norm)
+                cabi.debug("attn_tune", "0"), self.qkv_bias, self.qk_norm, self._ntk is not None)
         with _STEP_TUNE_LOCK:
             if skey not in _STEP_TUNE_CACHE:
                 _STEP_TUNE_CACHE[skey] = self._refine_timed(mclass, T, n_probe, ctx)
@@ -480,6 +511,9 @@ class KernelDecisions:
         for n, c in choice.items():
             if n == "attn":
                 self.attn_cfg[mclass] = tuple(c)
+                continue
+            if n == "wqkv_rope":
+                self.qkv_rope[mclass] = bool(c)
                 continue
             self.gemm_cfg[(n, mclass)] = c
             if (n, mclass) in self.gemm_times:          # bench.py's report: the isolated time of the chosen SHAPE (whatever ring the step preferred)
@@ -605,6 +639,21 @@ class KernelDecisions:
                     top = " ".join(f"{c}:{t * 1e3:.1f}" for c, t in sorted(times.items(), key=lambda kv: kv[1])[:6])
                     print(f"[tune-step] {name}:{mclass} rows={T} isolated choice {inc} {times.get(inc, float('nan')) * 1e3:.1f} us/layer -> {pick} "
                           f"{times[pick] * 1e3:.1f} | {top}", file=sys.stderr, flush=True)
+            # the qkv launch's tail: RoPE + the KV append in the GEMM's epilogue against the RoPE launch, where the qkv decision allows it - a challenger
+            # like any other (it must win by > 0.3 %)
+            saved_rope = self.qkv_rope.get(mclass, False)
+            self.qkv_rope[mclass] = True
+            fusable = self.use_qkv_rope(mclass, self.gemm_cfg[("wqkv", mclass)]) and cabi.debug("qkv_rope") is None
+            self.qkv_rope[mclass] = saved_rope
+            if fusable:
+                def apply_rope(cand):
+                    self.qkv_rope[mclass] = cand
+                times = measure([False, True], apply_rope)
+                pick = bool(times.get(True, float("inf")) < times.get(False, float("inf")) * 0.997)
+                choice["wqkv_rope"] = pick
+                log["wqkv_rope"] = {"in_step_choice": pick, "ms_per_layer_two_launches": round(times.get(False, float("nan")), 5),
+                                    "ms_per_layer_fused": round(times.get(True, float("nan")), 5)}
+                self.qkv_rope[mclass] = pick                # the attention coordinate below is measured with it
             # the attention launch: work-group rows, split rule
             inc = self.attn_cfg[mclass]
 
@@ -631,6 +680,8 @@ class KernelDecisions:
             self.layers = all_layers
             self._refining = False
             self.attn_events = saved_ev
+            if "wqkv_rope" in choice:
+                self.qkv_rope[mclass] = saved_rope
             if "attn" not in choice:
                 if saved_attn is None:
                     self.attn_cfg.pop(mclass, None)
