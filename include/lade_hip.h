@@ -52,7 +52,8 @@
  *                            their input (the reduction is fused into the consumer); lade_rope_kv_append carries the qkv epilogue of
  *                            Qwen2 (q / k / v bias) and Qwen3 (per-head RMSNorm of q and k before RoPE) - the reference adapts Llama only
  *   lade_gen_ctl_init / lade_gen_ctl_update / lade_gen_argmax / lade_gen_rows   HF's repetition penalty and min-length processors on the
- *                            step's rows; lade_greedy_post_step takes a set of EOS ids (the reference refuses them, lade/decoding.py:968)
+ *                            step's rows; lade_gen_constraints_init adds HF's bad_words_ids / suppress_tokens / begin_suppress_tokens /
+ *                            sequence_bias processors to them (the reference refuses every logits processor, lade/decoding.py:968); lade_greedy_post_step takes a set of EOS ids (the reference refuses them, lade/decoding.py:968)
  *   lade_emit_init / lade_emit_rows   the `scores` / `logits` tuples of generate(return_dict_in_generate=True): the reference refuses them
  *                            (lade/decoding.py:967 greedy, the matching assertion at the head of jacobi_sample_multilevel's loop for sampling)
  *   lade_time_attn / lade_time_attn_rot   hipEvent timing helpers for bench.py (no reference counterpart)
@@ -330,6 +331,7 @@ int lade_greedy_post_step(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* 
  *   gen[LADE_GEN_MIN_LEN]      absolute minimum length (min_length, or prompt length + min_new_tokens; 0 = off)
  *   gen[LADE_GEN_N_EOS], gen[LADE_GEN_EOS + e]   the ids masked to -inf while a row's sequence length L < min_len
  *   gen[LADE_GEN_VOCAB]        V
+ *   gen[LADE_GEN_CONS], gen[LADE_GEN_CONS + 1]   address of the token-constraint block (below), low / high 32 bits; 0 = no constraints
  *   gen[LADE_GEN_SEEN ..]      seen-set bitmap, ceil(V/32) words: bit t = token t occurs in prompt + accepted tokens */
 #define LADE_GEN_MAX_EOS 8
 #define LADE_GEN_PENALTY 0
@@ -341,20 +343,71 @@ int lade_greedy_post_step(int32_t* ctl, int32_t* window, int32_t wcap, int32_t* 
 #define LADE_GEN_SEEN 16
 #define LADE_GEN_WORDS(V) (LADE_GEN_SEEN + ((V) + 31) / 32)
 #define LADE_GEN_MAX_VOCAB (1 << 18)    /* a row's penalised set is staged in LDS: <= 32 KiB */
+#define LADE_GEN_CONS 5                 /* gen[5..6]: device address of the token-constraint block, low / high word (0 = none) */
+
+/* ---- token constraints (HF's SuppressTokensLogitsProcessor, SuppressTokensAtBeginLogitsProcessor, SequenceBiasLogitsProcessor,
+ * NoBadWordsLogitsProcessor) ----
+ * A second device block of int32 words `cons` (LADE_GEN_CONS_WORDS(V)), attached to `gen` by its address in gen[LADE_GEN_CONS ..+1]:
+ * the row kernels read that address at replay, so attaching, detaching or rewriting the block needs no re-capture.  Address 0: the row
+ * kernels compute exactly what they compute without this section.
+ *   cons[LADE_CONS_N_SEQ]       sequence entries in the table (<= LADE_GEN_MAX_SEQ)
+ *   cons[LADE_CONS_N_ONE]       how many of them, at the head of the table, have length 1 (they fire on every row, window rows included)
+ *   cons[LADE_CONS_BEGIN_INDEX] the input length at which the begin bans apply (-1 = no begin bans)
+ *   cons[LADE_CONS_FLAGS]       LADE_CONS_F_ADD: a sequence-bias class is present, so every score takes HF's `scores + bias` (bias +0.0
+ *                               where nothing fires: a -0.0 score becomes +0.0, as in HF)
+ *   cons[LADE_CONS_TAIL_N], cons[LADE_CONS_TAIL ..]   the last min(len, LADE_GEN_MAX_SEQ_LEN - 1) tokens of prompt + accepted tokens,
+ *                               right-aligned in LADE_GEN_MAX_SEQ_LEN - 1 slots
+ *   cons[LADE_CONS_OFF ..]      n_seq + 1 offsets into the token array; entry e = tokens [off[e], off[e+1]) = (t_0 .. t_{n-1}), n <= LADE_GEN_MAX_SEQ_LEN
+ *   cons[LADE_CONS_BIAS ..]     fp32 bits of the entries' biases (finite or -inf)
+ *   cons[LADE_CONS_TOK ..]      the entries' tokens, packed
+ *   cons[LADE_CONS_BAN ..]      ban bitmap, ceil(V/32) words: bit t = token t is -inf on every row; behind it the begin-ban bitmap, the
+ *                               same size: bit t = token t is -inf on a row whose input length L == begin_index
+ * Table order: the length-1 entries first, then the longer ones, each group in the order of HF's dict - the order in which HF's
+ * SequenceBiasLogitsProcessor sums them (length_1_bias, then the dict's longer entries). */
+#define LADE_GEN_MAX_SEQ_LEN 16         /* tokens of one sequence entry */
+#define LADE_GEN_MAX_SEQ 1024           /* sequence entries (length-1 -inf entries live in the ban bitmap and do not count) */
+#define LADE_GEN_CONS_MAX_VOCAB (3 << 16)   /* with constraints a row stages a second bitmap and the fired entries in LDS: <= 64 KiB */
+#define LADE_CONS_N_SEQ 0
+#define LADE_CONS_N_ONE 1
+#define LADE_CONS_BEGIN_INDEX 2
+#define LADE_CONS_FLAGS 3
+#define LADE_CONS_TAIL_N 4
+#define LADE_CONS_TAIL 8
+#define LADE_CONS_OFF (LADE_CONS_TAIL + LADE_GEN_MAX_SEQ_LEN)
+#define LADE_CONS_BIAS (LADE_CONS_OFF + LADE_GEN_MAX_SEQ + 8)
+#define LADE_CONS_TOK (LADE_CONS_BIAS + LADE_GEN_MAX_SEQ)
+#define LADE_CONS_BAN (LADE_CONS_TOK + LADE_GEN_MAX_SEQ * LADE_GEN_MAX_SEQ_LEN)
+#define LADE_GEN_CONS_WORDS(V) (LADE_CONS_BAN + 2 * (((V) + 31) / 32))
+#define LADE_CONS_F_ADD 1
 
 /* Writes the block: penalty (> 0, double: the value HF holds) / min_len (>= 0) / the min-length EOS ids (host array, n_eos <= LADE_GEN_MAX_EOS), and the seen set =
- * the n_prompt prompt tokens (device).  Once per sequence, before its first step. */
+ * the n_prompt prompt tokens (device).  Once per sequence, before its first step.  Detaches a constraint block (gen[LADE_GEN_CONS ..] = 0). */
 int lade_gen_ctl_init(int32_t* gen, int32_t V, double penalty, int32_t min_len, const int32_t* eos_ids, int32_t n_eos,
                       const int32_t* prompt, int32_t n_prompt, void* stream);
-/* Adds the tokens the last post-step accepted (ctl[LADE_CTL_HITS ..], ctl[LADE_CTL_N_ACCEPT] of them) to the seen set: after every
- * post-step, inside a captured step too (no host round trip). */
+/* Writes the constraint block `cons` and attaches it to `gen`: once per sequence, after lade_gen_ctl_init, in place (no re-capture).
+ * Host arrays: ban_ids[n_ban] (-inf on every row; no cap; ids >= V are ignored, as HF's isin does), begin_ids[n_begin] with begin_index
+ * (-inf on a row of input length L == begin_index), and the sequence entries in HF's dict order: seq_off[n_seq + 1] offsets into seq_tok,
+ * seq_bias[n_seq] (finite or -inf; NaN and +inf are refused).  add_bias != 0: a SequenceBias / NoBadWords class is present
+ * (LADE_CONS_F_ADD).  prompt (device, n_prompt tokens) seeds the tail.  LADE_E_ARG with the cap in the message for n_seq >
+ * LADE_GEN_MAX_SEQ, an entry longer than LADE_GEN_MAX_SEQ_LEN tokens or V > LADE_GEN_CONS_MAX_VOCAB.  Synchronises the stream (the host
+ * arrays are staged and copied). */
+int lade_gen_constraints_init(int32_t* gen, int32_t* cons, int32_t V, const int32_t* ban_ids, int32_t n_ban, const int32_t* begin_ids,
+                              int32_t n_begin, int32_t begin_index, const int32_t* seq_off, const int32_t* seq_tok, const float* seq_bias,
+                              int32_t n_seq, int32_t add_bias, const int32_t* prompt, int32_t n_prompt, void* stream);
+/* Adds the tokens the last post-step accepted (ctl[LADE_CTL_HITS ..], ctl[LADE_CTL_N_ACCEPT] of them) to the seen set, and shifts them
+ * into the tail of an attached constraint block: after every post-step, inside a captured step too (no host round trip). */
 int lade_gen_ctl_update(int32_t* gen, const int32_t* ctl, void* stream);
 /* Row argmax of one step under the controls.  logits [rows][ld] (model dtype), rows = [out row | n_inp window rows | candidate rows, gs
  * positions each]; candidate slots c >= ctl[LADE_CTL_G] are padding (am = 0, nothing else written).  Row r predicts the token at sequence
  * length L = pos[sel ? sel[r] : r] + 1 (pos / sel: the step's position ids and row selection, device).  Penalised set: the seen set,
  * plus guess[c][0..j] for position j of candidate c; window rows use the seen set alone (they feed the window and the pool, never an
  * emitted token).  Per row in fp32: s -> s < 0 ? s * p : s * inv once per distinct token of the set, then -inf for the EOS ids when
- * L < min_len; am[r] = the argmax in torch.argmax's order.  One pass over the logits, no fp32 copy. */
+ * L < min_len; am[r] = the argmax in torch.argmax's order.  One pass over the logits, no fp32 copy.
+ * With a constraint block attached, per row: first the sequence-bias sum - an entry (t_0 .. t_{n-1}) -> b fires on a row with L >= n whose
+ * last n-1 input_ids (the tail, then guess[c][0..j]) equal t_0 .. t_{n-2}; the fp32 sum per end token starts at 0 and takes the fired
+ * entries in table order, and is added to the score in one add - then the penalty, then -inf for the ban bitmap, for the begin-ban bitmap
+ * when L == begin_index, and for the min-length EOS ids.  Window rows take the ban bitmap and the length-1 entries only.  One work-group
+ * thread per entry resolves the row's fired entries into LDS before the pass. */
 int lade_gen_argmax(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t dtype, int32_t n_inp, int32_t gs,
                     const int32_t* gen, const int32_t* ctl, const int32_t* guess, const int32_t* pos, const int32_t* sel,
                     int32_t* am, void* stream);

@@ -29,6 +29,13 @@ MAX_LEVEL, MAX_WINDOW, MAX_GUESS_SET = 16, 128, 64
 REC_WORDS = 8 + MAX_LEVEL
 # generation-control block (include/lade_hip.h: LADE_GEN_*)
 GEN_MAX_EOS, GEN_SEEN, GEN_MAX_VOCAB = 8, 16, 1 << 18
+# token-constraint block (include/lade_hip.h: LADE_CONS_*, LADE_GEN_CONS*)
+GEN_CONS, GEN_MAX_SEQ_LEN, GEN_MAX_SEQ, GEN_CONS_MAX_VOCAB = 5, 16, 1024, 3 << 16
+CONS_N_SEQ, CONS_N_ONE, CONS_BEGIN_INDEX, CONS_FLAGS, CONS_TAIL_N, CONS_TAIL = 0, 1, 2, 3, 4, 8
+CONS_OFF = CONS_TAIL + GEN_MAX_SEQ_LEN
+CONS_BIAS = CONS_OFF + GEN_MAX_SEQ + 8
+CONS_TOK = CONS_BIAS + GEN_MAX_SEQ
+CONS_BAN = CONS_TOK + GEN_MAX_SEQ * GEN_MAX_SEQ_LEN
 # emitted-rows descriptor (include/lade_hip.h: LADE_EMIT_*), int64 words
 EMIT_SCORES, EMIT_LOGITS, EMIT_CAP, EMIT_LD, EMIT_COUNT, EMIT_WORDS = 0, 1, 2, 3, 4, 8
 
@@ -36,6 +43,11 @@ EMIT_SCORES, EMIT_LOGITS, EMIT_CAP, EMIT_LD, EMIT_COUNT, EMIT_WORDS = 0, 1, 2, 3
 def gen_words(V: int) -> int:
     """int32 words of the generation-control block of a vocabulary of V (LADE_GEN_WORDS)"""
     return GEN_SEEN + (V + 31) // 32
+
+
+def gen_cons_words(V: int) -> int:
+    """int32 words of the token-constraint block of a vocabulary of V (LADE_GEN_CONS_WORDS)"""
+    return CONS_BAN + 2 * ((V + 31) // 32)
 
 
 def record_seal(rec, step_no: int) -> int:
@@ -109,6 +121,7 @@ SIGNATURES = {
     "lade_greedy_post_step": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp,
                               _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "lade_gen_ctl_init": [_vp, _i32, C.c_double, _i32, _vp, _i32, _vp, _i32, _vp],
+    "lade_gen_constraints_init": [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp],
     "lade_gen_ctl_update": [_vp, _vp, _vp],
     "lade_gen_argmax": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lade_gen_rows": [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -33,14 +33,41 @@ COLOR_PRINT = int(os.environ.get("COLOR_PRINT", 0))
 class GenControls:
     """HF's RepetitionPenaltyLogitsProcessor and min-length family as the device step applies them (include/lade_hip.h, "generation
     controls").  penalty: HF's `repetition_penalty` (1.0 = off).  min_len: absolute minimum sequence length, `min_length` or prompt length
-    + `min_new_tokens` (0 = off).  min_len_eos: the ids masked while a row is shorter than min_len (None: the stopping EOS set)."""
+    + `min_new_tokens` (0 = off).  min_len_eos: the ids masked while a row is shorter than min_len (None: the stopping EOS set).
+    Token constraints (include/lade_hip.h, "token constraints"; HF's suppress_tokens / begin_suppress_tokens / sequence_bias /
+    bad_words_ids).  ban: ids that are -inf on every row.  begin_ban / begin_index: ids that are -inf on a row whose input length equals
+    begin_index.  sequence_bias: ((t_0, .., t_{n-1}), bias) entries in the order of HF's dict, bias finite or -inf (a banned word of
+    more than one token is a -inf entry; a single banned token belongs in `ban`).  add_bias: a SequenceBias / NoBadWords processor is
+    present, so every score passes through HF's `scores + bias` (implied by a non-empty sequence_bias)."""
     penalty: float = 1.0
     min_len: int = 0
     min_len_eos: Optional[tuple] = None
+    ban: tuple = ()
+    begin_ban: tuple = ()
+    begin_index: int = -1
+    sequence_bias: tuple = ()
+    add_bias: bool = False
+
+    def __post_init__(self):
+        if len(self.sequence_bias) > cabi.GEN_MAX_SEQ:
+            raise cabi.LadeHipError(f"{len(self.sequence_bias)} sequence_bias / bad_words_ids entries: the device step takes at most "
+                                    f"{cabi.GEN_MAX_SEQ} (LADE_GEN_MAX_SEQ; single banned tokens do not count)")
+        for seq, bias in self.sequence_bias:
+            if not 1 <= len(seq) <= cabi.GEN_MAX_SEQ_LEN:
+                raise cabi.LadeHipError(f"a sequence_bias / bad_words_ids entry of {len(seq)} tokens: the device step takes 1 to "
+                                        f"{cabi.GEN_MAX_SEQ_LEN} (LADE_GEN_MAX_SEQ_LEN)")
+            if bias != bias or bias == float("inf"):
+                raise cabi.LadeHipError(f"sequence_bias {tuple(seq)} -> {bias}: a bias is finite or -inf")
+        if self.begin_ban and self.begin_index < 0:
+            raise cabi.LadeHipError(f"begin_suppress_tokens with begin_index={self.begin_index}")
+
+    @property
+    def constrained(self) -> bool:
+        return bool(self.ban or self.begin_ban or self.sequence_bias or self.add_bias)
 
     @property
     def active(self) -> bool:
-        return self.penalty != 1.0 or self.min_len > 0
+        return self.penalty != 1.0 or self.min_len > 0 or self.constrained
 
 
 def eos_set(eos_token_id) -> tuple:
@@ -275,6 +302,7 @@ class LookaheadDecoder:
         self._s = None                    # the sampling run's warper, RNGs and forced-hits buffers (sample_start)
         # allocated on first use: a decoder that never gets controls / never samples holds neither
         self._gen = None                  # generation-control block (start)
+        self._cons = None                 # token-constraint block, attached to _gen by its address (start)
         self._smp = None                  # pinned and device sampling buffers (_sampling_buffers)
         self._draw_warm = False           # the device draw's torch kernels have run once (sample_start)
         # per-token scores / logits (start(emit=...)): the request, the run's buffers, the device descriptor the captured steps read
@@ -311,7 +339,7 @@ class LookaheadDecoder:
     @_on_device
     def start(self, prompt: Sequence[int], eos_token_id=None, rng: Optional[random.Random] = None,
               controls: Optional[GenControls] = None, emit=None, emit_cap: int = 0) -> None:
-        """eos_token_id: an int, a sequence of ints or None.  controls: GenControls (repetition penalty / min length) or None; with None,
+        """eos_token_id: an int, a sequence of ints or None.  controls: GenControls (repetition penalty / min length / token constraints) or None; with None,
         at most one EOS id and no emit request a step launches exactly the kernels of the plain step.
         emit: None, or one or both of "scores" / "logits": every step appends the fp32 rows that decided its tokens to per-run buffers of
         emit_cap rows (emit_capacity); emitted() returns them."""
@@ -334,8 +362,12 @@ class LookaheadDecoder:
                 self._gen = torch.zeros(cabi.gen_words(st.V), dtype=torch.int32, device=e.device)
             c = self.controls
             mask_eos = self.eos_set if c.min_len_eos is None else eos_set(c.min_len_eos)
-            ops.gen_ctl_init(self._gen, st.V, c.penalty, c.min_len if mask_eos else 0, mask_eos,
-                             torch.tensor(self.prompt, dtype=torch.int32, device=e.device))
+            prompt_d = torch.tensor(self.prompt, dtype=torch.int32, device=e.device)
+            ops.gen_ctl_init(self._gen, st.V, c.penalty, c.min_len if mask_eos else 0, mask_eos, prompt_d)      # (detaches the last run's constraints)
+            if c.constrained:               # rewritten in place per sequence: the captured steps find it through _gen
+                if self._cons is None:
+                    self._cons = torch.zeros(cabi.gen_cons_words(st.V), dtype=torch.int32, device=e.device)
+                ops.gen_constraints_init(self._gen, self._cons, st.V, c.ban, c.begin_ban, c.begin_index, c.sequence_bias, c.add_bias, prompt_d)
         self.emit, self._emit_bufs, self._emit_src = emit_request(emit), {}, None
         if self.emit is not None:
             if self._emit_desc is None:
@@ -491,6 +523,8 @@ class LookaheadDecoder:
         state = (st.ctl, st.window, st.pool_cnt, st.pool_tok, st.guess, st.tail) + (() if e.ntk_state is None else (e.ntk_state,))
         if self.controls is not None:
             state += (self._gen,)           # the warm-up's post-step adds its tokens to the seen set
+            if self._cons is not None:
+                state += (self._cons,)      # ... and shifts them into an attached constraint block's tail
         if self.emit is not None and not forward_only:
             state += (self._emit_desc,)     # ... and its lade_emit_rows advances the row counter (the rows it wrote are overwritten by the real step)
         for gcap in self._buckets():
@@ -598,7 +632,8 @@ class LookaheadDecoder:
             # the lookahead-parallel verify and EOS scan (lade_lp_reduce_apply) know neither the controls nor an EOS set
             if controls is not None and controls.active:
                 raise cabi.LadeHipError("lookahead parallelism (DIST_WORKERS > 1 / FORCE_LP) does not implement repetition_penalty / "
-                                        "min_length / min_new_tokens: run on one GPU without FORCE_LP")
+                                        "min_length / min_new_tokens / bad_words_ids / suppress_tokens / begin_suppress_tokens / "
+                                        "sequence_bias: run on one GPU without FORCE_LP")
             eos = eos_set(eos_token_id)
             if len(eos) > 1:
                 raise cabi.LadeHipError(f"lookahead parallelism (DIST_WORKERS > 1 / FORCE_LP) stops on one EOS id only, got {list(eos)}: "

@@ -275,30 +275,59 @@ def _check_admitted(warpers):
 
 def controls_from_processors(processors):
     """Splits HF's logits-processor list into what the device step applies and the rest: (GenControls or None, remaining).
-    Taken: RepetitionPenaltyLogitsProcessor (without prompt_ignore_length), MinLengthLogitsProcessor, MinNewTokensLengthLogitsProcessor.
+    Taken: RepetitionPenaltyLogitsProcessor (without prompt_ignore_length), MinLengthLogitsProcessor, MinNewTokensLengthLogitsProcessor,
+    and the token constraints SuppressTokensLogitsProcessor, SuppressTokensAtBeginLogitsProcessor (one begin index), NoBadWordsLogitsProcessor
+    and SequenceBiasLogitsProcessor (one with finite biases) - read from the processor objects, so HF's own filtering of `[eos]` out of
+    bad_words_ids holds.  Single-token -inf entries join the suppressed ids; everything else becomes a sequence entry, in the dicts' order.
     Everything else stays in `remaining` (the warpers of a sampling call, `admitted_warpers`, or a processor the callers refuse as
     before).  HF applies processors before warpers; a taken processor placed after a warper is refused (AssertionError), since the
-    device step applies the controls to the raw logits."""
+    device step applies the controls to the raw logits.  The device step adds the sequence biases before the penalty (where HF's
+    generate() puts them): finite biases placed after a RepetitionPenaltyLogitsProcessor are refused the same way (-inf absorbs the
+    penalty, so the bans may sit on either side)."""
     from transformers.generation import logits_process as lp
     warper_kinds = admitted_warpers()
+    neg_inf = -float("inf")
     penalty, min_len, mask_eos, rest = 1.0, 0, None, []
+    ban, begin_ban, begin_index, entries, add_bias, finite_taken, penalty_seen = [], (), -1, [], False, False, False
     for p in (processors or []):
         kind = type(p)
+        finite = kind is lp.SequenceBiasLogitsProcessor and any(b != neg_inf for b in p.sequence_bias.values())
         taken = ((kind is lp.RepetitionPenaltyLogitsProcessor and not getattr(p, "prompt_ignore_length", None) and penalty == 1.0)
                  or (kind in (lp.MinLengthLogitsProcessor, lp.MinNewTokensLengthLogitsProcessor)
-                     and (mask_eos is None or eos_set(p.eos_token_id) == mask_eos)))
+                     and (mask_eos is None or eos_set(p.eos_token_id) == mask_eos))
+                 or kind in (lp.SuppressTokensLogitsProcessor, lp.NoBadWordsLogitsProcessor)
+                 or (kind is lp.SuppressTokensAtBeginLogitsProcessor and (not begin_ban or int(p.begin_index) == begin_index))
+                 or (kind is lp.SequenceBiasLogitsProcessor and not (finite and finite_taken)))
+        penalty_seen |= kind is lp.RepetitionPenaltyLogitsProcessor
         if not taken:
             rest.append(p)
             continue
         assert not any(type(q) in warper_kinds for q in rest), \
-            f"{kind.__name__} after a logits warper: lookahead applies repetition_penalty / min length before the warpers (HF's order)"
+            (f"{kind.__name__} after a logits warper: lookahead applies repetition_penalty / min length / bad_words_ids / suppress_tokens / "
+             "begin_suppress_tokens / sequence_bias before the warpers (HF's order)")
         if kind is lp.RepetitionPenaltyLogitsProcessor:
             penalty = float(p.penalty)
+        elif kind is lp.SuppressTokensLogitsProcessor:
+            ban += [int(t) for t in p.suppress_tokens.tolist()]
+        elif kind is lp.SuppressTokensAtBeginLogitsProcessor:
+            begin_ban = tuple(begin_ban) + tuple(int(t) for t in p.begin_suppress_tokens.tolist())
+            begin_index = int(p.begin_index)
+        elif kind in (lp.NoBadWordsLogitsProcessor, lp.SequenceBiasLogitsProcessor):
+            assert not (finite and penalty_seen), \
+                ("SequenceBiasLogitsProcessor with finite biases after RepetitionPenaltyLogitsProcessor: lookahead adds sequence_bias before "
+                 "the repetition penalty (HF's order)")
+            finite_taken |= finite
+            add_bias = True
+            for seq, bias in p.sequence_bias.items():
+                if len(seq) == 1 and bias == neg_inf:
+                    ban.append(int(seq[0]))
+                else:
+                    entries.append((tuple(int(t) for t in seq), float(bias)))
         else:
             mask_eos = eos_set(p.eos_token_id)
             need = p.min_length if kind is lp.MinLengthLogitsProcessor else p.prompt_length_to_skip + p.min_new_tokens
             min_len = max(min_len, int(need))
-    ctl = GenControls(penalty, min_len, mask_eos)
+    ctl = GenControls(penalty, min_len, mask_eos, tuple(ban), tuple(begin_ban), begin_index, tuple(entries), add_bias)
     return (ctl if ctl.active else None), rest
 
 
@@ -411,7 +440,7 @@ def jacobi_greedy_search_multilevel(self, input_ids, logits_processor=None, stop
     """Same call contract as lade/decoding.py:697-715 (extras `chat`, `stop_token`); returns LongTensor [1, len], or with
     return_dict_in_generate HF's GenerateDecoderOnlyOutput with `scores` / `logits` (the reference asserts that off, :967)."""
     request = output_request(generation_config, return_dict_in_generate, output_scores, output_logits, output_attentions, output_hidden_states)
-    controls, logits_processor = controls_from_processors(logits_processor)       # repetition penalty / min length run on the device
+    controls, logits_processor = controls_from_processors(logits_processor)       # repetition penalty / min length / token constraints run on the device
     assert logits_processor is None or len(logits_processor) == 0, "logits processors are not supported in greedy lookahead (:968)"
     if max_length is not None:
         from transformers.generation.stopping_criteria import MaxLengthCriteria, StoppingCriteriaList

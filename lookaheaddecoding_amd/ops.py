@@ -507,7 +507,7 @@ rope_kv_append_ex = rope_kv_append
 rope_kv_append_parts_ex = rope_kv_append_parts
 
 
-# ---- generation controls (repetition penalty, min length; include/lade_hip.h "generation controls") -------------------------------
+# ---- generation controls (repetition penalty, min length, token constraints; include/lade_hip.h "generation controls") -------------------------------
 def host_ids(ids) -> "C.Array":
     """a host int32 array for the entry points that copy a short id list into their launch (EOS sets)"""
     import ctypes as C
@@ -518,6 +518,27 @@ def gen_ctl_init(gen: torch.Tensor, V: int, penalty: float, min_len: int, eos_id
     """penalty / min_len / the min-length EOS ids into the control block, seen set = the prompt tokens (device int32)"""
     assert gen.dtype == torch.int32 and gen.numel() >= cabi.gen_words(V) and prompt.dtype == torch.int32
     call("lade_gen_ctl_init", ptr(gen), V, float(penalty), int(min_len), host_ids(eos_ids), len(eos_ids), ptr(prompt), prompt.numel())
+
+
+def gen_constraints_init(gen: torch.Tensor, cons: torch.Tensor, V: int, ban, begin_ban, begin_index: int, sequence_bias, add_bias: bool,
+                         prompt: torch.Tensor) -> None:
+    """Writes the token-constraint block `cons` (int32 [cabi.gen_cons_words(V)]) and attaches it to `gen` (lade_gen_constraints_init):
+    ban / begin_ban id lists, sequence_bias = ((tokens, bias), ...) in HF's dict order, prompt (device int32) seeds the tail.  After
+    gen_ctl_init, once per sequence."""
+    import numpy as np
+    assert gen.dtype == torch.int32 and cons.dtype == torch.int32 and cons.numel() >= cabi.gen_cons_words(V) and prompt.dtype == torch.int32
+    ban_a = np.asarray(list(ban), dtype=np.int32).reshape(-1)
+    begin_a = np.asarray(list(begin_ban), dtype=np.int32).reshape(-1)
+    off = np.zeros(len(sequence_bias) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(seq) for seq, _ in sequence_bias], dtype=np.int64)
+    tok = np.asarray([t for seq, _ in sequence_bias for t in seq], dtype=np.int32).reshape(-1)
+    bias = np.asarray([b for _, b in sequence_bias], dtype=np.float32).reshape(-1)
+
+    def host(a):
+        return a.ctypes.data if a.size else None
+
+    call("lade_gen_constraints_init", ptr(gen), ptr(cons), V, host(ban_a), ban_a.size, host(begin_a), begin_a.size, int(begin_index),
+         off.ctypes.data, host(tok), host(bias), len(sequence_bias), int(bool(add_bias or len(sequence_bias))), ptr(prompt), prompt.numel())
 
 
 def gen_ctl_update(gen: torch.Tensor, ctl: torch.Tensor) -> None:

@@ -3,13 +3,18 @@
     python tools/gen_controls_bench.py [--steps K] [--warmup W] [--rounds R]
     python tools/gen_controls_bench.py --loop off|on      # one steady greedy loop only (for rocprofv3 --kernel-trace --stats)
     python tools/gen_controls_bench.py --kernel           # lade_gen_argmax alone against lade_argmax_rows, 16 and 76 rows
+    python tools/gen_controls_bench.py --constraints      # the step with token constraints on top of the penalty, against the penalty alone
 
 At the c2 shape (llama2-7b, W15 N5 G15) and qwen2.5-7b, bf16, random weights, 128-token prompt, hipGraph steps: the host clock around
 K steps with the controls off (the plain step: lm_head argmax epilogue) and on (repetition_penalty 1.05: the lm_head materialises the
 logits, lade_gen_argmax reads them once, lade_gen_ctl_update after the post-step), alternated R times.  Prints one JSON line per preset
 with the medians, on / off and the logits rows of the steps that were timed (1 + W + the candidate bucket's rows).
 `--kernel`: hipEvent time of lade_gen_argmax (penalty 1.05, a 2048-token seen set) and of lade_argmax_rows on bf16 rows of V = 32000 and
-152064, at 16 rows (no candidates) and 76 rows (W15 N5 G15 with all 15 candidates)."""
+152064, at 16 rows (no candidates) and 76 rows (W15 N5 G15 with all 15 candidates); and of lade_gen_rows (the sampling path: it also
+stores the processed fp32 rows) with the penalty alone and with the constraint block attached.
+`--constraints`: the same alternating rounds with both arms under repetition_penalty 1.05, one of them with 64 suppressed ids and 32
+sequence entries of 2 to 4 tokens (half of them -inf, a quarter built from the prompt's own n-grams so that they can fire): one graph
+serves both arms, the block is rewritten in place."""
 from __future__ import annotations
 
 import argparse
@@ -30,6 +35,22 @@ from lookaheaddecoding_amd.weights import make_config, random_weights_torch  # n
 
 PRESETS = ("llama2-7b", "qwen2.5-7b")
 ON = GenControls(penalty=1.05)
+
+
+def constrained(V: int, prompt, penalty: float = 1.05) -> GenControls:
+    """the constraints arm: 64 suppressed ids, 32 sequence entries of length 2 to 4 (every other one -inf, every fourth from the prompt)"""
+    g = torch.Generator().manual_seed(7)
+    ban = tuple(torch.randint(3, V, (64,), generator=g).tolist())
+    entries = []
+    for e in range(32):
+        n = 2 + e % 3
+        if e % 4 == 0:
+            at = int(torch.randint(0, len(prompt) - n, (1,), generator=g))
+            seq = tuple(int(t) for t in prompt[at:at + n])
+        else:
+            seq = tuple(torch.randint(3, V, (n,), generator=g).tolist())
+        entries.append((seq, -float("inf") if e % 2 else (-4.0 if e % 4 else 2.5)))
+    return GenControls(penalty=penalty, ban=ban, sequence_bias=tuple(entries), add_bias=True)
 
 
 def _timed(dec, prompt, controls, steps, warmup, rows=None):
@@ -64,10 +85,23 @@ def kernel(reps: int) -> None:
             guess = torch.randint(0, V, (max(g, 1) * gs,), dtype=torch.int32, device="cuda")
             pos = torch.arange(2000, 2000 + rows, dtype=torch.int32, device="cuda")
             am = torch.zeros(rows, dtype=torch.int32, device="cuda")
-            runs = {"gen_argmax": lambda: ops.gen_argmax(logits, W, gs, gen, ctl, guess, pos, None, am),
-                    "argmax_rows": lambda: ops.argmax_rows(logits, out=am)}
+            rows_out = torch.empty(rows - W, V, dtype=torch.float32, device="cuda")
+            cons = torch.zeros(cabi.gen_cons_words(V), dtype=torch.int32, device="cuda")
+            c = constrained(V, seen.tolist())
+
+            def attach(on):
+                ops.gen_ctl_init(gen, V, 1.05, 0, [2], seen)
+                if on:
+                    ops.gen_constraints_init(gen, cons, V, c.ban, c.begin_ban, c.begin_index, c.sequence_bias, c.add_bias, seen)
+
+            runs = {"gen_argmax": (False, lambda: ops.gen_argmax(logits, W, gs, gen, ctl, guess, pos, None, am)),
+                    "argmax_rows": (False, lambda: ops.argmax_rows(logits, out=am)),
+                    "gen_rows": (False, lambda: ops.gen_argmax(logits, W, gs, gen, ctl, guess, pos, None, am, rows_out)),
+                    "gen_argmax_constrained": (True, lambda: ops.gen_argmax(logits, W, gs, gen, ctl, guess, pos, None, am)),
+                    "gen_rows_constrained": (True, lambda: ops.gen_argmax(logits, W, gs, gen, ctl, guess, pos, None, am, rows_out))}
             res = {}
-            for name, fn in runs.items():
+            for name, (on, fn) in runs.items():
+                attach(on)
                 for _ in range(10):
                     fn()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -78,7 +112,9 @@ def kernel(reps: int) -> None:
                 torch.cuda.synchronize()
                 res[name] = round(e0.elapsed_time(e1) / reps * 1e3, 2)
             print(json.dumps({"measure": "kernel", "V": V, "rows": rows, "candidates": g, "dtype": "bf16", "reps": reps,
-                              "gen_argmax_us": res["gen_argmax"], "argmax_rows_us": res["argmax_rows"]}), flush=True)
+                              "gen_argmax_us": res["gen_argmax"], "argmax_rows_us": res["argmax_rows"], "gen_rows_us": res["gen_rows"],
+                              "gen_argmax_constrained_us": res["gen_argmax_constrained"],
+                              "gen_rows_constrained_us": res["gen_rows_constrained"]}), flush=True)
 
 
 def main():
@@ -89,6 +125,7 @@ def main():
     ap.add_argument("--loop", choices=("off", "on"), default=None)
     ap.add_argument("--presets", default=",".join(PRESETS))
     ap.add_argument("--kernel", action="store_true")
+    ap.add_argument("--constraints", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     a = ap.parse_args()
     if a.kernel:
@@ -104,6 +141,26 @@ def main():
         if a.loop is not None:
             ms, tps = _timed(dec, prompt, ON if a.loop == "on" else None, a.steps, a.warmup)
             print(json.dumps({"measure": "loop", "preset": preset, "controls": a.loop, "ms_per_step": round(ms, 3)}), flush=True)
+        elif a.constraints:
+            cons_arm = constrained(cfg["vocab"], prompt)
+            on, con, tok_on, tok_con, rows = [], [], [], [], []
+            _timed(dec, prompt, ON, a.steps, a.warmup)          # (capture and first-use costs stay out of both arms)
+            for _ in range(a.rounds):
+                ms, tps = _timed(dec, prompt, ON, a.steps, a.warmup)
+                on.append(ms)
+                tok_on.append(tps)
+                ms, tps = _timed(dec, prompt, cons_arm, a.steps, a.warmup, rows)
+                con.append(ms)
+                tok_con.append(tps)
+            m_on, m_con = statistics.median(on), statistics.median(con)
+            print(json.dumps({"measure": "constraints_step", "preset": preset, "W": 15, "N": 5, "G": 15, "graph": True, "steps": a.steps,
+                              "rounds": a.rounds, "suppressed_ids": len(cons_arm.ban), "sequence_entries": len(cons_arm.sequence_bias),
+                              "penalty_only_ms_per_step": round(m_on, 3), "constrained_ms_per_step": round(m_con, 3),
+                              "constrained_over_penalty_only": round(m_con / m_on, 4),
+                              "penalty_only_tokens_per_step": round(statistics.median(tok_on), 3),
+                              "constrained_tokens_per_step": round(statistics.median(tok_con), 3),
+                              "penalty_only_all": [round(x, 3) for x in on], "constrained_all": [round(x, 3) for x in con],
+                              "constrained_logits_rows": {str(r): rows.count(r) for r in sorted(set(rows))}}), flush=True)
         else:
             off, on, tok_off, tok_on, rows = [], [], [], [], []
             for _ in range(a.rounds):
